@@ -9,8 +9,10 @@ One STEP = one decode pass of the hot path over the rank's batch: (z_hat, symbol
 hyper-synthesis -> y_hat = symbols + mu -> two-layer synthesis -> uint8 pixels, for a Kodak-24-shaped
 synthetic set (18 x 512x768 + 6 x 768x512; mshyper/configs/two_layer_syn.py, random-init weights --
 there is no network for Kodak or checkpoints).  Weak scaling: every rank decodes its own set.
-The JSON line also carries the encode+decode rate, the (bpp, PSNR) of the set, the live-measured
+A plain run sets up, warms up, times the K steps and prints the headline line.  With --full the JSON line
+also carries the encode+decode rate, the (bpp, PSNR) of the set, the other regions, the live-measured
 roofline of the dominant kernel and a CPU baseline (torch-CPU port of the same decode, rank 0, N=1).
+--dump-outputs DIR writes the uint8 pixels of the last timed step as float32 .npy files (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -71,6 +73,36 @@ def host_cpu():
     except OSError:
         pass
     return model, (len(cores) or os.cpu_count())
+
+
+DUMP_BUDGET_BYTES = 60 << 20      # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_outputs(outs, out_dir):
+    """--dump-outputs: what the timed path returned in its last step -- the uint8 pixels [n, H, W, 3] of every batch of the set,
+    in the step's order -- as ``pixels<i>_<n>x<H>x<W>.npy`` (float32).  A batch that does not fit its share of the byte budget
+    (the budget is split evenly, a smaller batch's unused share going to the larger ones) is written as a fixed sample instead:
+    ``pixels<i>_<n>x<H>x<W>_sample.npy``, the values at sorted flat indices drawn from a seeded generator, the same on every run."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    sizes = [t.numel() for t in outs]
+    caps, left = {}, DUMP_BUDGET_BYTES // 4
+    pending = sorted(range(len(outs)), key=lambda i: sizes[i])
+    while pending:
+        share = left // len(pending)
+        if sizes[pending[0]] > share:
+            caps.update((i, share) for i in pending)
+            break
+        i = pending.pop(0)
+        caps[i] = sizes[i]
+        left -= sizes[i]
+    for i, t in enumerate(outs):
+        a = t.cpu().numpy()
+        name = f"pixels{i}_" + "x".join(str(d) for d in a.shape[:3])
+        if caps[i] < a.size:
+            idx = np.sort(np.random.default_rng(2024 + i).choice(a.size, caps[i], replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(out_dir / f"{name}.npy", a.astype(np.float32))
 
 
 def _free_port():
@@ -192,7 +224,16 @@ def main():
                     help="A/B: skip the step-level choice of the decode launches' schedules (ops.tune_step on the two-stream step)")
     ap.add_argument("--launch-check", action="store_true",
                     help="only rendezvous the ranks and run the path's collectives (no kernels); prints a dry-run line")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline as well: the one-rank RCCL group at N = 1, the sustained rate, the "
+                         "regions (encode, encode+decode, W1, training, evaluate, bf16 x 3, SGA, bitstream), (bpp, PSNR), the "
+                         "roofline tables and the CPU baseline.  Off: set-up, warm-up, the timed steps and the line only")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write the pixels of the last timed step to DIR/<name>.npy (float32, rank 0, "
+                         "under 64 MB in all; larger batches as a fixed seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # not under torchrun: be the launcher (no GPU call before this)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -219,7 +260,7 @@ def main():
 
     assert torch.cuda.is_available(), "bench.py needs an MI355X; there is no CPU fallback for the hot path"
     rccl_note = None
-    if int(os.environ.get("WORLD_SIZE", 1)) == 1 and not os.environ.get("SNTC_DIST_BACKEND"):
+    if args.full and int(os.environ.get("WORLD_SIZE", 1)) == 1 and not os.environ.get("SNTC_DIST_BACKEND"):
         # N = 1: still form a ONE-rank RCCL group, so that the barrier / max-reduce / all-gather of the timed path run through
         # RCCL on the GPU (the only RCCL evidence a one-GPU box can give).  If RCCL cannot initialise here the bench carries
         # on without a group and says so in `rccl`.
@@ -372,11 +413,12 @@ def main():
 
     rank_walls = []
 
-    def timed(fn, steps, warmup, stats=None, headline=False):
+    def timed(fn, steps, warmup, stats=None, headline=False, last=None):
         """The contract's timing: W untimed warm-up steps, then EXACTLY K steps bracketed by a barrier +
         torch.cuda.synchronize() on both sides, MAX over ranks of the wall time.  ``stats`` (a dict) additionally receives
         the per-step durations from HIP events recorded on the launch stream after every step (hipEvents,
-        median + min) -- every step joins its side streams back into the current stream before it returns."""
+        median + min) -- every step joins its side streams back into the current stream before it returns.  ``last`` (a
+        list) receives what the last timed step returned."""
         for _ in range(warmup):
             fn()
         D.barrier()
@@ -386,7 +428,10 @@ def main():
         if evs:
             evs[0].record()
         for i in range(steps):
-            fn()
+            if last is not None and i == steps - 1:
+                last.append(fn())
+            else:
+                fn()
             if evs:
                 evs[i + 1].record()
         torch.cuda.synchronize()
@@ -463,7 +508,7 @@ def main():
     # (The hyper-synthesis plans are shared by encode and decode: what the encode pass below measures for them with the device
     # to itself is then re-judged by the decode step's own clock -- see `decode_tuning` further down.)
     enc_fn = w1_x = w1_step = None
-    if not args.decode_only:
+    if args.full and not args.decode_only:
         enc_fn = lambda: on_streams(lambda b: model.encode(b[1], check=False))
         w1_x = synthetic_batch(64, 256, 256, 4321 + rank, dev)   # encode+decode on the synthetic 256x256 batches the north star asks for
 
@@ -508,13 +553,17 @@ def main():
     # ran 40 more untimed steps first and still reported `warmup: W`: ADVICE r5.  The device reaches its sustained clock only after
     # ~40 ms of uninterrupted load -- behind a tuning pass whose samples end in host synchronisations the first eight timed steps ran
     # 3.54, 3.33, 3.27, 3.23, 3.19, 3.14, 3.12, 3.10 ms before settling at 3.09 -- so that ramp is now INSIDE `value`.)
-    hst = {}
-    t_dec = timed(decode_step, args.steps, args.warmup, hst, headline=True)   # the headline: exactly --steps steps after --warmup
+    hst, last_out = {}, []
+    t_dec = timed(decode_step, args.steps, args.warmup, hst, headline=True, last=last_out)   # the headline: exactly --steps steps after --warmup
     ms_per_step = 1e3 * t_dec / args.steps
     ms_by_rank = [round(1e3 * w / args.steps, 4) for w in rank_walls]   # each rank's own clock over the same K steps (value uses the max)
     value = world * pixels_per_step * args.steps / t_dec / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_out[0], args.dump_outputs)
+    del last_out
+    # Everything below up to the line is --full only: a plain run is set-up, warm-up, the timed steps and the line.
     # ... and the sustained rate is reported NEXT to it, under its own name: PREHEAT + W untimed steps, then K timed ones
-    PREHEAT = 0 if args.no_preheat else 40
+    PREHEAT = 0 if args.no_preheat or not args.full else 40
     sustained = None
     if PREHEAT:
         sst = {}
@@ -535,8 +584,9 @@ def main():
         return out, t / steps
 
     regions = {}
-    regions["decode"], _ = region(decode_step, R_STEPS, pixels_per_step, decode_eager)
-    if not args.decode_only:
+    if args.full:
+        regions["decode"], _ = region(decode_step, R_STEPS, pixels_per_step, decode_eager)
+    if args.full and not args.decode_only:
         regions["encode"], _ = region(enc_fn, R_STEPS_ENC, pixels_per_step)
         regions["encode_decode_score"], t_e2e_step = region(e2e_step, R_STEPS_ENC, pixels_per_step)
         e2e_value = regions["encode_decode_score"]["mpixels_per_s"]
@@ -705,7 +755,7 @@ def main():
             ops.PROFILE = None
         return per_kernel
 
-    if rank == 0:
+    if rank == 0 and args.full:
         per_kernel = kernel_table(decode_eager, 3)
         name, k = max(per_kernel.items(), key=lambda kv: kv[1]["ms"])
         achieved = k["flops"] / (k["ms"] * 1e-3) / 1e12
@@ -770,7 +820,7 @@ def main():
 
     # ---- CPU baseline: the torch-CPU port of the same decode on this box's host cores ---------------
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.decode_only:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.decode_only:
         from oracle import model_np, torch_ref
         ref_model = model_np.Model(cfg["transform_config"], rd_lambda=cfg["rd_lambda"])
         weights = model.get_weights()

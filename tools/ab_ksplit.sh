@@ -6,13 +6,14 @@
 #     $(ls build/*.o | grep -v conv_plan.o) /tmp/conv_plan_$v.o; done
 # Result of round 6: profiles/r06_ab_ksplit.txt (the threshold stays at 32).
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R; mkdir -p gpurun_out
+T=$(mktemp -d)
 for i in 1 2; do
 for lib in hip k16 k8; do
   export SNTC_LIB=$R/shallow-ntc_amd/lib/libsntc_$lib.so
-  python bench.py --workload w1 --decode-only --no-cpu-baseline --steps 20 --warmup 5 --tuning-file '' > gpurun_out/ab_ks.json 2> gpurun_out/ab_ks.err
+  python bench.py --full --workload w1 --decode-only --no-cpu-baseline --steps 20 --warmup 5 --tuning-file '' > $T/ab_ks.json 2> $T/ab_ks.err
   python - <<PY
 import json
-d=json.loads(open('gpurun_out/ab_ks.json').read().strip().split('\n')[-1])
+d=json.loads(open('$T/ab_ks.json').read().strip().split('\n')[-1])
 print('$lib: W1 decode', d['value'], 'Mpx/s', d['ms_per_step'], 'ms; region median', d['regions']['decode']['ms_per_step'])
 PY
   python - <<PY

@@ -21,7 +21,7 @@ for i in 1 2; do
       set -- $spec
       echo "$lib: $(python $R/tools/one_layer.py --kind $1 --k $2 --s $3 --cin $4 --cout $5 --n $6 --hw $7 $8 --reps 8 2>&1 | grep TFLOP | tail -1)"
     done
-    python $R/bench.py --decode-only > $O/b.json 2> $O/b.err
+    python $R/bench.py --full --decode-only > $O/b.json 2> $O/b.err
     python -c "
 import json; d=json.load(open('$O/b.json')); print('$lib: bench decode', d['value'], 'Mpx/s', d['ms_per_step'], 'ms; region median', d['regions']['decode']['ms_per_step'])"
   done

@@ -9,11 +9,11 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_$TAG; rm -rf $O; mkdir -p $O
 SQ="GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT"
 # ---- decode (the headline region): one stream, so that a kernel's duration is its own; the launches are the ones bench.py's
 # two-stream step settles on (ops.tune_step) -- measured ONCE here, unprofiled, and applied from the file in the profiled runs
-python3 $R/bench.py --decode-only --no-cpu-baseline --steps 5 --warmup 2 --retune --write-tuning $O/decode_tuning.json > $O/decode_tuning_run.json 2> /dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/dec_stats -- python3 $R/bench.py --decode-only --streams 1 --steps 20 --warmup 3 --tuning-file $O/decode_tuning.json > $O/decode_only_bench.json 2> $O/dec_stats.err
-rocprofv3 --pmc $SQ --output-format csv -d $O/dec_pmc_sq -- python3 $R/bench.py --decode-only --streams 1 --steps 5 --warmup 2 --tuning-file $O/decode_tuning.json > /dev/null 2> $O/dec_pmc_sq.err
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/dec_pmc_fetch -- python3 $R/bench.py --decode-only --streams 1 --steps 5 --warmup 2 --tuning-file $O/decode_tuning.json > /dev/null 2> $O/dec_pmc_fetch.err
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/dec_pmc_write -- python3 $R/bench.py --decode-only --streams 1 --steps 5 --warmup 2 --tuning-file $O/decode_tuning.json > /dev/null 2> $O/dec_pmc_write.err
+python3 $R/bench.py --full --decode-only --no-cpu-baseline --steps 5 --warmup 2 --retune --write-tuning $O/decode_tuning.json > $O/decode_tuning_run.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/dec_stats -- python3 $R/bench.py --full --decode-only --streams 1 --steps 20 --warmup 3 --tuning-file $O/decode_tuning.json > $O/decode_only_bench.json 2> $O/dec_stats.err
+rocprofv3 --pmc $SQ --output-format csv -d $O/dec_pmc_sq -- python3 $R/bench.py --full --decode-only --streams 1 --steps 5 --warmup 2 --tuning-file $O/decode_tuning.json > /dev/null 2> $O/dec_pmc_sq.err
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/dec_pmc_fetch -- python3 $R/bench.py --full --decode-only --streams 1 --steps 5 --warmup 2 --tuning-file $O/decode_tuning.json > /dev/null 2> $O/dec_pmc_fetch.err
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/dec_pmc_write -- python3 $R/bench.py --full --decode-only --streams 1 --steps 5 --warmup 2 --tuning-file $O/decode_tuning.json > /dev/null 2> $O/dec_pmc_write.err
 # ---- encode (ELIC analysis + hyper transforms): the layer table script launches every layer of encode and decode
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/enc_stats -- python3 $R/tools/profile_layers.py --reps 5 > $O/layer_table_profiled.txt 2> $O/enc_stats.err
 rocprofv3 --pmc $SQ --output-format csv -d $O/enc_pmc_sq -- python3 $R/tools/profile_layers.py --reps 3 > /dev/null 2> $O/enc_pmc_sq.err
@@ -36,8 +36,8 @@ python3 tools/ab_encode.py --one-stream >> $O/ab_encode_rgb.txt 2>&1
 python3 tools/microbench/write_bw.py > $O/write_bw.txt 2>&1
 python3 tools/syn_block.py > $O/synthesis_vs_layers.txt 2>&1
 python3 tools/syn_block.py --ch 24 --res 0 5 76 76 >> $O/synthesis_vs_layers.txt 2>&1
-python3 bench.py --decode-only --steps 50 --warmup 10 --set-decode > $O/decode_only_set_decode.json 2> /dev/null
-python3 bench.py --decode-only --steps 50 --warmup 10 --streams 1 > $O/decode_only_one_stream.json 2> /dev/null
+python3 bench.py --full --decode-only --steps 50 --warmup 10 --set-decode > $O/decode_only_set_decode.json 2> /dev/null
+python3 bench.py --full --decode-only --steps 50 --warmup 10 --streams 1 > $O/decode_only_one_stream.json 2> /dev/null
 python3 tools/stream_kernels.py > $O/stream_kernels.txt 2>&1
 python3 tools/time_evaluate.py > $O/evaluate_b1.txt 2>&1
 python3 tools/profile_layers.py --reps 5 --precision bf16x3 > $O/layer_table_bf16x3.txt 2>&1
@@ -49,7 +49,7 @@ python3 tools/ab_order.py > $O/ab_order.txt 2>&1
 python3 tools/summarize_pmc.py ${TAG}_pmc_summary $(find $O/dec_stats -name "*kernel_stats.csv" | head -1) $O/dec_pmc_sq $O/dec_pmc_fetch $O/dec_pmc_write > $O/summary_dec.txt 2>&1
 python3 tools/summarize_pmc.py ${TAG}_encode_pmc_summary $(find $O/enc_stats -name "*kernel_stats.csv" | head -1) $O/enc_pmc_sq $O/enc_pmc_fetch $O/enc_pmc_write > $O/summary_enc.txt 2>&1
 # (the summaries above carry the hashes of the kernel sources they were measured on: the bench line below reads them, traffic_stale false)
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cp profiles/${TAG}_pmc_summary.json profiles/${TAG}_encode_pmc_summary.json $O/
 for d in dec enc sga bits; do cp $(find $O/${d}_stats -name "*kernel_stats.csv" | head -1) $O/${d}_kernel_stats.csv; done
 ls $O

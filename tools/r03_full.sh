@@ -3,7 +3,7 @@ R=${GRAFT_REPO_ROOT:-.}; O=$R/gpurun_out/r03_full; mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -x -q > $O/gpu_tests.txt 2>&1; echo "pytest rc=$?" >> $O/gpu_tests.txt
 tail -6 $O/gpu_tests.txt
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 python - <<'PY'
 import json,os
 O=os.environ.get("GRAFT_REPO_ROOT",".")+"/gpurun_out/r03_full"

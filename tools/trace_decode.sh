@@ -2,7 +2,7 @@
 # kernel + memory-copy trace of a few serial decode steps: which small launches sit between the convolutions?
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/trace_decode; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/tr -- python3 $R/bench.py --decode-only --streams 1 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench.json 2> $O/err.txt
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/tr -- python3 $R/bench.py --full --decode-only --streams 1 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench.json 2> $O/err.txt
 python3 - <<'PY'
 import csv, glob, os
 O=os.environ["GRAFT_REPO_ROOT"]+"/gpurun_out/trace_decode"

@@ -2,7 +2,7 @@
 # kernel trace (start / end timestamps per stream) of the default two-stream decode: which launches really run side by side?
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/trace_two; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --output-format csv -d $O/tr -- python3 $R/bench.py --decode-only --steps 4 --warmup 2 > $O/bench.json 2> $O/err.txt
+rocprofv3 --kernel-trace --output-format csv -d $O/tr -- python3 $R/bench.py --full --decode-only --steps 4 --warmup 2 > $O/bench.json 2> $O/err.txt
 python3 - <<'PY'
 import csv, glob, os
 O=os.environ["GRAFT_REPO_ROOT"]+"/gpurun_out/trace_two"
