@@ -248,3 +248,60 @@ def test_many_blobs_of_mixed_sizes_in_any_order(dev):
         for i, px in zip(order, got):
             assert torch.equal(px, want[i]), f"blob {i} in order {list(order)}"
     assert ops.stream_k_enabled() == was                   # the static-schedule blocks left the process-wide switch as they found it
+
+
+# csrc/rans.hip kRansLdsLimit: a table set larger than this (table_bytes = 8 per table + 2 per cdf entry) is read from global memory
+# by rans_encode_kernel<false> / rans_decode_kernel<false> instead of being staged in LDS
+RANS_LDS_LIMIT = 150 * 1024 - (2 * 16 * 64 * 2 + 2 * 16 * 64 * 4)
+
+
+def test_table_set_beyond_the_lds_limit(dev, monkeypatch):
+    """A table set too large for LDS: the global-table encoder gives the words of the LDS-staged encoder on data that only uses the
+    first 64 tables (the same tables in both sets), the words of the Python restatement on data that uses every table, and the
+    global-table decoder (binary search of cdf, no start tables) gives the data back exactly."""
+    from shallow_ntc_amd import entropy_coding as ec
+    rng = np.random.default_rng(41)
+    small = ec.normal_tables()
+    extra = []
+    for k in range(20):                      # wide two-sided geometric tables, 3001 ... 4901 symbols + escape
+        half = 1500 + 100 * k
+        v = np.arange(-half, half + 1)
+        extra.append((-half, ec.quantize_pmf(np.exp(-np.abs(v) / (50.0 + 40 * k)), 2.0 ** -12)))
+    big = small + extra
+    table_bytes = lambda tabs: 8 * len(tabs) + 4 * ((sum(len(f) for _, f in tabs) + 1) // 2)
+    assert table_bytes(small) <= RANS_LDS_LIMIT < table_bytes(big)
+    ds, db = ec.DeviceTables(small, dev), ec.DeviceTables(big, dev)
+    monkeypatch.setattr(ec, "USE_START_TABLES", False)       # the decoder's table search of rans_decode_kernel<LDS>
+    n, P, c = 2, 67, 13
+    E = P * c
+    sig = np.array([0.11 * np.exp(ec.SCALE_FACTOR * k) for k in range(64)])
+    # (1) ids < 64: LDS-staged and global-table instances code the same tables -> the same words; both decode exactly
+    tids = rng.integers(0, 64, size=(n, P, c)).astype(np.int16)
+    vals = np.rint(rng.laplace(0, 1, size=(n, P, c)) * sig[tids] * 1.5).astype(np.int32)
+    vals[0, 5, 2], vals[1, 60, 0] = 25000, -30000              # escapes
+    td, vd = torch.from_numpy(tids).to(dev), torch.from_numpy(vals).to(dev)
+    for segs, lanes in ((1, 64), (3, 16)):
+        p_lds, l_lds = ec.rans_encode(vd, td, ds, segs, lanes)
+        p_glb, l_glb = ec.rans_encode(vd, td, db, segs, lanes)
+        np.testing.assert_array_equal(l_glb, l_lds)
+        assert torch.equal(p_glb, p_lds), (segs, lanes)
+        for dt in (ds, db):
+            np.testing.assert_array_equal(ec.rans_decode(p_glb, l_glb, td, (n, P, c), dt, segs, lanes).cpu().numpy(), vals)
+    # (2) ids over every table of the large set: words of the Python restatement, exact round trip
+    tids = rng.integers(0, len(big), size=(n, P, c)).astype(np.int16)
+    scale = np.where(tids < 64, sig[np.minimum(tids, 63)] * 1.5, 50.0 + 40 * (tids - 64))
+    vals = np.rint(rng.laplace(0, 1, size=(n, P, c)) * scale).astype(np.int32)
+    vals[1, 1, 1], vals[0, 66, 12] = 32000, -32000
+    td, vd = torch.from_numpy(tids).to(dev), torch.from_numpy(vals).to(dev)
+    for segs, lanes in ((1, 64), (2, 8)):
+        payload, lens = ec.rans_encode(vd, td, db, segs, lanes)
+        words = payload.cpu().numpy().view(np.uint16)
+        off = np.concatenate([[0], np.cumsum(lens)])
+        eseg = -(-(-(-E // segs)) // 64) * 64
+        for b in range(n):
+            for g in range(segs):
+                s = b * segs + g
+                sl = slice(g * eseg, min(E, (g + 1) * eseg))
+                ref = rans_np.encode_stream(vals[b].ravel()[sl], tids[b].ravel()[sl], big, lanes)
+                assert words[off[s]:off[s + 1]].tolist() == ref, (segs, lanes, b, g)
+        np.testing.assert_array_equal(ec.rans_decode(payload, lens, td, (n, P, c), db, segs, lanes).cpu().numpy(), vals)

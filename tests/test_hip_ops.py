@@ -874,3 +874,88 @@ def test_prior_tail_selection_hand_kats_on_the_gpu(dev):
         _, bits, sym = ops.entropy_scale_normal(dev_t(y, dev), dev_t(hyper, dev), want_symbols=True)
         assert int(sym.flatten()[0]) == int(v)
         assert abs(float(bits[0]) / c - want) <= 2e-4 * want, (v, float(bits[0]) / c, want)
+
+
+@pytest.mark.parametrize("c", [4, 8, 12, 16, 24, 32, 48])
+def test_gdn_small_every_channel_count(c, dev):
+    """Every gdn_small_kernel<C> instance (csrc/pixel.hip), forward and inverse, (alpha, epsilon) = (1, 1) and (2, 0.5), on a pixel
+    count that is not a multiple of the 256-thread block; against the float64 oracle."""
+    from shallow_ntc_amd import ops
+    rng = np.random.default_rng(1000 + c)
+    npix = 2 * 256 + 37                     # two full 256-thread blocks and a partial one
+    x = rng.standard_normal((1, 1, npix, c)).astype(np.float32)
+    beta = (0.5 + rng.random(c)).astype(np.float32)
+    gamma = (0.1 * np.eye(c) + 0.05 * rng.random((c, c))).astype(np.float32)
+    xd, bd, gd = dev_t(x, dev), dev_t(beta, dev), dev_t(gamma, dev)
+    for inverse in (False, True):
+        for alpha, eps in ((1, 1.0), (2, 0.5)):
+            got = ops.gdn_small(xd, bd, gd, inverse, alpha, eps).cpu().numpy()
+            ref = O.gdn(x, beta, gamma, inverse, alpha, eps)
+            assert np.abs(got - ref).max() <= TOL * max(np.abs(ref).max(), 1.0), (inverse, alpha, eps)
+
+
+@pytest.mark.parametrize("ch", [12, 24, 48])
+@pytest.mark.parametrize("has_res", [False, True])
+def test_two_layer_tail_every_activation(ch, has_res, dev):
+    """two_layer_tail_kernel<CH> for every activation kind (0 none, 1 igdn, 2 gdn, 3 relu, 4 leaky relu), with and without the
+    residual half, at a latent size that is not a multiple of the 16-pixel tile: the float form against float64, the fused-pixel
+    form (crops smaller than the reconstruction) against the float form followed by the pixel kernel."""
+    from shallow_ntc_amd import ops
+    rng = np.random.default_rng(ch * 10 + has_res)
+    n, hh, wh = 2, 13, 11
+    t = (rng.standard_normal((n, hh, wh, ch * (2 if has_res else 1))) * 0.5).astype(np.float32)
+    beta = (1.0 + rng.random(ch)).astype(np.float32)
+    gamma = (0.1 * np.eye(ch) + 0.02 * rng.random((ch, ch))).astype(np.float32)
+    w2 = (rng.standard_normal((5, 5, 3, ch)) * 0.1).astype(np.float32)
+    b2 = (rng.standard_normal(3) * 0.1).astype(np.float32)
+    td, bd, gd, wd, b2d = (dev_t(a, dev) for a in (t, beta, gamma, w2, b2))
+    acts = {0: lambda v: v, 1: lambda v: O.gdn(v, beta, gamma, inverse=True), 2: lambda v: O.gdn(v, beta, gamma, inverse=False),
+            3: O.relu, 4: O.leaky_relu}
+    for kind, act in acts.items():
+        hsum = act(t[..., :ch].astype(np.float64)) + (t[..., ch:] if has_res else 0.0)
+        ref = O.conv2d_transpose(hsum, w2, b2, 2)
+        recon = ops.two_layer_tail(td, ch, has_res, kind, bd, gd, wd, b2d)
+        got = recon.cpu().numpy()
+        assert got.shape == ref.shape
+        assert np.abs(got - ref).max() <= TOL * max(np.abs(ref).max(), 1.0), kind
+        for h, w in ((2 * hh - 1, 2 * wh - 5), (7, 3)):
+            refpx = dev_t(rng.uniform(-0.5, 0.5, (n, h, w, 3)).astype(np.float32), dev)
+            sse_want, px_want = ops.pixels_sse(refpx, recon, want_pixels=True)
+            px, sse = ops.two_layer_tail_pixels(td, ch, has_res, kind, bd, gd, wd, b2d, h, w, reference=refpx)
+            assert torch.equal(px, px_want) and torch.equal(sse, sse_want), (kind, h, w)
+
+
+@pytest.mark.parametrize("h,w", [(37, 53), (171, 166)])
+def test_image_quality_one_channel(h, w, dev):
+    """ssim_scale_kernel<1>: one-channel images, below 160 (single-scale SSIM) and above (MS-SSIM), against float64."""
+    from shallow_ntc_amd import ops
+    rng = np.random.default_rng(h * w)
+    yy, xx = np.mgrid[0:h, 0:w]
+    a = np.clip(np.rint(128 + 70 * np.sin(xx / 9) * np.cos(yy / 7) + rng.normal(0, 6, size=(2, h, w))), 0, 255)[..., None]
+    b = np.clip(np.rint(a + rng.normal(0, 9, size=a.shape)), 0, 255)
+    a, b = a.astype(np.float32), b.astype(np.float32)
+    ref, _ = O.image_quality(a, b)
+    got = ops.image_quality(dev_t(a, dev), dev_t(b, dev))
+    np.testing.assert_allclose(got, ref, rtol=3e-5)
+
+
+@pytest.mark.parametrize("cout", [128, 192, 256])
+@pytest.mark.parametrize("k", [5, 3])
+def test_rgb_conv_every_instance(cout, k, dev):
+    """rgb_conv_kernel<NT, KH, act> for every column-tile case of its launch switch (128, 192, default: 256) x kernel size (the
+    5 x 5 instance and the generic one) x activation (none; relu and leaky relu share the other instance), on a ragged image,
+    against the float64 oracle."""
+    from shallow_ntc_amd import ops
+    s = 2
+    for act in (None, "relu", "leaky_relu"):
+        if not ops.RgbConvPlan.supported(k, s, 3, cout, act):
+            pytest.fail(f"rgb_conv instance not offered: k={k} s={s} cout={cout} act={act}")
+        rng = np.random.default_rng(k * 1000 + cout + len(str(act)))
+        n, h, w = 2, 37, 29
+        x = rng.standard_normal((n, h, w, 3)).astype(np.float32)
+        wk = (rng.standard_normal((k, k, 3, cout)) * 0.2).astype(np.float32)
+        b = rng.standard_normal(cout).astype(np.float32)
+        ref = O.ACTIVATIONS[act](O.conv2d(x, wk, b, s))
+        got = ops.RgbConvPlan(dev_t(wk, dev), dev_t(b, dev), s, act)(dev_t(x, dev)).cpu().numpy()
+        assert got.shape == ref.shape
+        assert np.abs(got - ref).max() <= TOL * max(np.abs(ref).max(), 1.0), act

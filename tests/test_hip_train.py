@@ -506,3 +506,25 @@ def test_train_eval_loop_and_itinf_loop_drivers(dev, tmp_path):
     tm, vm, variables = itinf_lib.itinf_on_data_batch(dict(num_steps=20, log_metrics_every_steps=5, eval_every_steps=10), None, None, sga, batches[0])
     assert [r["step"] for r in tm] == [0, 5, 10, 15] and [r["step"] for r in vm] == [10, 20]
     assert set(variables) == {"z_loc", "y_loc"} and variables["y_loc"].shape == (2, 4, 4, 32)
+
+
+@pytest.mark.parametrize("cout", [32, 64, 96, 128, 160, 192])
+def test_conv_wgrad_gather_side_every_tile_width(cout, dev):
+    """wgrad_kernel<WN, TN, false> (gathered side Cs % 4 != 0) for every column-tile width of its launch switch (wg_pick_bn: 32, 64,
+    96, 128, 160, default 192), and colsum_kernel<false> (bias gradient, C % 4 != 0), against the float64 restatement."""
+    from shallow_ntc_amd import ops
+    k, s, cin, n, h, w = 3, 1, 33, 2, 9, 7
+    rng = np.random.default_rng(cout)
+    x = rng.standard_normal((n, h, w, cin)).astype(np.float32)
+    wt = torch.tensor(rng.standard_normal((k, k, cin, cout)) * 0.1, dtype=torch.float64, requires_grad=True)
+    bt = torch.zeros(cout, dtype=torch.float64, requires_grad=True)
+    y = train_ref.conv2d(train_ref.as_input(x), wt, bt, s)
+    g = rng.standard_normal((n, y.shape[2], y.shape[3], cout)).astype(np.float32)
+    (y * train_ref.as_input(g)).sum().backward()
+    dw = torch.full((k, k, cin, cout), 7.0, dtype=torch.float32, device=dev)
+    ops.conv_wgrad("conv", k, s, cin, cout, torch.from_numpy(x).to(dev), torch.from_numpy(g).to(dev), dw)
+    assert _rel(dw.cpu().numpy(), wt.grad.numpy()) < 2e-5
+    gx = rng.standard_normal((n, h, w, cin)).astype(np.float32)          # a gradient with 33 channels: colsum_kernel<false>
+    db = torch.empty((cin,), dtype=torch.float32, device=dev)
+    ops.bias_grad(torch.from_numpy(gx).to(dev), db)
+    assert _rel(db.cpu().numpy(), gx.astype(np.float64).reshape(-1, cin).sum(0)) < 2e-5
