@@ -26,7 +26,6 @@
 // hold it to the same 2e-5-vs-float64 bar.  Reference: the arithmetic of tf.nn.conv2d / conv2d_transpose behind
 // common/transforms.py:209-232,298-361 (hyper-synthesis, syntheses).
 #include <algorithm>
-#include <mutex>
 #include <type_traits>
 #include "sntc_internal.h"
 
@@ -923,10 +922,10 @@ __global__ void __launch_bounds__(256) split3_kernel(const float* __restrict__ x
 }
 
 // ---------------------------------------------------------------------------------------------
-// variants + launch (ids continue csrc/gather_gemm.hip's: 11 = 256 x 256, 12 = 256 x 128, 13 = 256 x 192 -- the exact fit of the
-// N = 192 layers, which lose a quarter of either of the others to padding; all 512 threads, one workgroup per CU)
+// the kernels of tile variants 11 = 256 x 256, 12 = 256 x 128, 13 = 256 x 192 (the exact fit of the N = 192 layers, which lose a
+// quarter of either of the others to padding) for the instance table of gather_gemm.hip
 // ---------------------------------------------------------------------------------------------
-static const void* bf3p_kernel(int v, bool halo) {
+const void* bf3p_kernel(int v, bool halo) {
   switch (v) {
     case 11: return halo ? reinterpret_cast<const void*>(&bf3_kernel<4, 2, 2, 4, true, false>) : reinterpret_cast<const void*>(&bf3_kernel<4, 2, 2, 4, false, false>);
     case 12: return halo ? reinterpret_cast<const void*>(&bf3_kernel<4, 2, 2, 2, true, true>) : reinterpret_cast<const void*>(&bf3_kernel<4, 2, 2, 2, false, false>);
@@ -935,50 +934,7 @@ static const void* bf3p_kernel(int v, bool halo) {
   }
 }
 
-int bf3p_variant_bm(int v) { return 256; }
-int bf3p_variant_bn(int v) { return v == 11 ? 256 : v == 13 ? 192 : 128; }
-size_t bf3p_sk_slab_floats(int v) { return (size_t)(v == 11 ? 8 : v == 13 ? 6 : 4) * 16 * 512; }
-
-static size_t bf3p_lds_bytes(int v, bool halo) {
-  const size_t rinfo = 2 * bf3p_variant_bm(v) * sizeof(int4);
-  if (halo) return (size_t)2 * kBf3PatchRounds * 512 * 16 + (size_t)(v == 12 ? kBf3DeepRing : 3) * bf3p_variant_bn(v) * 96 + rinfo;
-  return (size_t)3 * (bf3p_variant_bm(v) + bf3p_variant_bn(v)) * 96 + rinfo;
-}
 int bf3p_patch_rows_max() { return kBf3PatchRounds * 512 / 6; }
-
-static std::once_flag g_bf3p_once[16];
-static int g_bf3p_rc[16];
-
-int bf3p_init() {
-  int dev = 0;
-  SNTC_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 16) return fail(SNTC_ERR_UNSUPPORTED, "device index beyond the residency tables");
-  std::call_once(g_bf3p_once[dev], [&] {
-    g_bf3p_rc[dev] = SNTC_OK;
-    for (int v : {11, 12, 13})
-      for (bool halo : {false, true}) {
-        hipError_t e = hipFuncSetAttribute(bf3p_kernel(v, halo), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bf3p_lds_bytes(v, halo));
-        if (e != hipSuccess) g_bf3p_rc[dev] = hip_fail(e, "bf3p_init");
-      }
-  });
-  return g_bf3p_rc[dev];
-}
-
-int bf3p_launch(int variant, const GGArgs& args, int nblocks, hipStream_t stream) {
-  const bool halo = args.halo != 0;
-  const void* fn = bf3p_kernel(variant, halo);
-  if (!fn) return fail(SNTC_ERR_UNSUPPORTED, "unknown pre-split bf16 x 3 tile variant");
-  int rc = bf3p_init();
-  if (rc) return rc;
-  GGArgs a = args;
-#ifdef SNTC_DIAG
-  if (const char* e = getenv("SNTC_GG_DBG")) a.dbg = atoi(e);   // diagnostic builds only (make DIAG=1): results are WRONG with it
-#endif
-  void* params[] = {&a};
-  hipError_t e = hipLaunchKernel(fn, dim3(nblocks), dim3(512), params, bf3p_lds_bytes(variant, halo), stream);
-  if (e != hipSuccess) return hip_fail(e, "pre-split bf16 x 3 gather-GEMM launch");
-  return SNTC_OK;
-}
 
 }  // namespace sntc
 

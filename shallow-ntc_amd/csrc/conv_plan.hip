@@ -165,10 +165,14 @@ struct sntc_conv_plan {
 };
 typedef sntc_conv_plan::Choice TuneChoice;
 
+// the tile variants of a plan's family (fp32 or pre-split) are those with a compiled instance of the family's base form
+static const GGInstance* base_instance(const sntc_conv_plan* p, int v) {
+  return p->s3 ? gg_find(v, kLoadVec, kStageDma, kFormPresplit) : gg_find(v, kLoadVec, kStageRing, kFormPlain);
+}
+
 extern "C" int sntc_conv_plan_set_tile(sntc_conv_plan* p, int variant) {
   if (!p) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_plan_set_tile: null plan");
-  if (variant < 0 || variant > (p->s3 ? 13 : kNumVariants) || (p->s3 && variant != 0 && variant < 11))
-    return fail(SNTC_ERR_UNSUPPORTED, "sntc_conv_plan_set_tile: unknown tile variant");
+  if (variant != 0 && !base_instance(p, variant)) return fail(SNTC_ERR_UNSUPPORTED, "sntc_conv_plan_set_tile: unknown tile variant");
   p->tile = variant;
   return SNTC_OK;
 }
@@ -529,16 +533,15 @@ extern "C" int64_t sntc_conv_flops(const sntc_conv_plan* p, int n, int h, int w)
   return 2 * (int64_t)n * px * d.kh * d.kw * d.cin * d.cout;
 }
 
-// Launch schedule of one call: tile variant, split-K factor, and whether the persistent stream-K workers run it.
+// Launch schedule of one call: the instance it runs (tile variant, loader, stage path, form), split-K factor, and whether the
+// persistent stream-K workers run it.
 struct Sched {
-  int variant = 2;
+  const GGInstance* inst = nullptr;   // nullptr: no candidate passed the filters (a forced choice only)
   int ksplit = 1;
   bool sk = false;
   int workers = 0;        // stream-K: resident workgroups
   int64_t units = 0;      // sum over groups of tiles * stages
   int64_t blocks = 0;     // workgroups launched
-  bool deep = false;      // the deep-ring direct-to-LDS instance (small launches)
-  bool valid = false;     // some candidate passed the filters (always true without a forced choice)
 };
 
 static int max_steps(const sntc_conv_plan* p) {
@@ -568,11 +571,8 @@ static int pick_ksplit(const sntc_conv_plan* p, const Geo& g) {
   return std::max(1, std::min({8, want, std::max(1, steps_min / 8)}));
 }
 
-static int variant_bm(int v) { return v > kNumVariants ? bf3p_variant_bm(v) : gg_variant_bm(v); }
-static int variant_bn(int v) { return v > kNumVariants ? bf3p_variant_bn(v) : gg_variant_bn(v); }
-
-static void count_work(const sntc_conv_plan* p, int v, int64_t M, int64_t* tiles, int64_t* units, double* padded_macs) {
-  const int bm = variant_bm(v), bn = variant_bn(v);
+static void count_work(const sntc_conv_plan* p, const GGInstance& inst, int64_t M, int64_t* tiles, int64_t* units, double* padded_macs) {
+  const int bm = inst.bm, bn = inst.bn;
   const int64_t ntm = (M + bm - 1) / bm;
   *tiles = 0; *units = 0; *padded_macs = 0;
   for (int gi = 0; gi < p->ngroups; ++gi) {
@@ -599,16 +599,18 @@ static Sched schedule_s3(const sntc_conv_plan* p, const Geo& g, int64_t n, const
   Sched best;
   const int64_t M = n * g.Qh * g.Qw;
   const int msteps = max_steps(p);
-  const int cus = std::max(8, gg_num_cus());
   double best_cost = 1e300;
   for (int v : {11, 12, 13}) {
     if (p->tile >= 11 && v != p->tile) continue;
     if (force && v != force->variant) continue;
+    const GGInstance* inst = gg_find(v, kLoadVec, kStageDma, kFormPresplit);
+    if (!inst) continue;
+    const int cus = std::max(8, gg_resident(*inst));
     int64_t tiles, units;
     double macs;
-    count_work(p, v, M, &tiles, &units, &macs);
+    count_work(p, *inst, M, &tiles, &units, &macs);
     Sched s;
-    s.variant = v;
+    s.inst = inst;
     s.ksplit = 1;
     s.units = units;
     const int64_t fit = msteps > 0 ? units / msteps : 0;
@@ -617,7 +619,6 @@ static Sched schedule_s3(const sntc_conv_plan* p, const Geo& g, int64_t n, const
     // faster one workgroup per tile (160 vs 145 TFLOP/s-equivalent); few long ones need the stream-K cut (191 vs 155)
     const bool can_sk = g_stream_k_enabled.load(std::memory_order_relaxed) && units < (1LL << 31) && workers >= 8 && 2 * workers >= cus;
     s.sk = force ? (force->sk != 0 && can_sk) : (can_sk && !p->no_stream_k && (units >= 64 * tiles || p->force_stream_k));
-    s.valid = true;
     s.workers = s.sk ? workers : 0;
     s.blocks = s.sk ? workers : tiles;
     double cost = macs;
@@ -632,7 +633,29 @@ static Sched schedule_s3(const sntc_conv_plan* p, const Geo& g, int64_t n, const
     cost /= (v == 11 ? 1.0 : v == 13 ? 0.97 : 0.92);
     if (cost < best_cost) { best_cost = cost; best = s; }
   }
+  // patch staging: the taps of a slab sample the input at unit stride, and every group's patch (tile rows + the tap window's
+  // reach in flattened macro pixels + a zero row) fits the patch buffers; <= 32 taps (the kernel keeps one validity bit per tap
+  // and row)
+  bool halo = best.inst && !p->no_halo && g.sA == 1;
+  for (int gi = 0; halo && gi < p->ngroups; ++gi) {
+    const int th = p->g[gi].T / p->g[gi].tw;
+    halo = p->g[gi].T <= 32 && best.inst->bm + (th - 1) * g.Qw + p->g[gi].tw - 1 + (p->g[gi].T > 1 ? 1 : 0) <= bf3p_patch_rows_max();
+  }
+  if (halo) best.inst = gg_find(best.inst->variant, kLoadVec, kStageDma, kFormPresplitHalo);
   return best;
+}
+
+// fp32 stream-K unit order of a launch: column tile outermost (the COLM twin) for single-group plans whose packed weights do not
+// fit an XCD's 4 MB L2 -- the 3x3 hyper-synthesis layer (11 MB): HBM-side reads of the launch 1667 -> 857 MB.  The twin replaces
+// the strip-major 128 x 128 register-staged vector instance only where it keeps as many workgroups resident: the workers were
+// counted from that instance's residency.
+static const GGInstance* column_major(const sntc_conv_plan* p, const Sched& sc) {
+  const GGInstance* strip = sc.inst;
+  if (!sc.sk || strip->load != kLoadVec || strip->stage != kStageRing || strip->form != kFormPlain || p->ngroups != 1 || p->colm == 0 ||
+      (p->colm != 1 && (size_t)p->g[0].Ncol * p->g[0].K * sizeof(float) <= ((size_t)4 << 20)))
+    return nullptr;
+  const GGInstance* twin = gg_find(strip->variant, kLoadVec, kStageRing, kFormColm);
+  return twin && gg_resident(*twin) >= gg_resident(*strip) ? twin : nullptr;
 }
 
 static Sched schedule(const sntc_conv_plan* p, const Geo& g, int64_t n, bool fused = false, const TuneChoice* force = nullptr) {
@@ -642,22 +665,27 @@ static Sched schedule(const sntc_conv_plan* p, const Geo& g, int64_t n, bool fus
   const int ksplit = fused ? 1 : pick_ksplit(p, g);
   const int msteps = max_steps(p);
   const bool pro = p->d.prologue != SNTC_PRO_NONE;
+  const GGLoad load = !p->vec ? kLoadGather : pro ? kLoadVecPro : kLoadVec;
+  const GGForm form = fused ? kFormFuse2 : p->bf3 ? kFormBf3 : kFormPlain;
   double best_cost = 1e300;
   for (int v = 1; v <= kNumVariants; ++v) {
-    if (fused ? v != 3 : (p->tile >= 1 && p->tile <= kNumVariants && v != p->tile)) continue;
+    if (!fused && p->tile != 0 && v != p->tile) continue;
     // single-buffered fragments / one wave per SIMD: forced only.  (128 x 192 does beat 128 x 96 on the long N = 192
     // contractions when it has the device to itself -- 5x5 / 2, 192 -> 192: 130.9 vs 119.8 TFLOP/s -- but at two workgroups per
     // CU and 61 KB of LDS it shuts out the other stream's kernels: bench.py's two-stream encode went from 48.5 to 49.2 ms.)
     if (p->tile == 0 && (v == 6 || v == 7 || v == 10)) continue;
-    if (p->bf3 && v != 2 && v != 4) continue;                       // the bf16 x 3 experiment is instantiated for two tile shapes
     if (force && v != force->variant) continue;
+    // FUSE2 exists for variant 3 only, the bf16 x 3 experiment for variants 2 and 4; asked-for direct-to-LDS staging falls back
+    // to the register ring where a variant has no such instance (6, 7, 10)
+    const GGInstance* ring = gg_find(v, load, kStageRing, form);
+    if (!ring) continue;
+    const GGInstance* dma = !fused && plan_dma(p) ? gg_find(v, load, kStageDma, kFormPlain) : nullptr;
     int64_t tiles, units;
     double macs;
-    count_work(p, v, M, &tiles, &units, &macs);
-    const bool dma = !fused && plan_dma(p) && gg_resident_blocks_dma(v) > 0;
-    const int resident = std::max(1, fused ? gg_resident_blocks_fused() : p->bf3 ? gg_resident_blocks_bf3(v) : dma ? gg_resident_blocks_dma(v) : gg_resident_blocks(v, p->vec, pro));
+    count_work(p, *ring, M, &tiles, &units, &macs);
     Sched s;
-    s.variant = v;
+    s.inst = dma ? dma : ring;
+    const int resident = std::max(1, gg_resident(*s.inst));
     s.ksplit = ksplit;
     s.units = units;
     // stream-K when every resident worker gets at least one longest tile's worth of stages (then a tile is shared by at
@@ -677,18 +705,19 @@ static Sched schedule(const sntc_conv_plan* p, const Geo& g, int64_t n, bool fus
     const bool can_sk = ksplit == 1 && g_stream_k_enabled.load(std::memory_order_relaxed) && units < (1LL << 31) && workers >= 8 &&
                         2 * workers >= resident;
     s.sk = force ? (force->sk != 0 && can_sk) : (can_sk && !p->no_stream_k && !short_tiles);
-    s.valid = true;
     s.workers = s.sk ? workers : 0;
     s.blocks = s.sk ? workers : tiles * ksplit;
     double cost = macs;
     // a launch of about one workgroup per CU or fewer has nothing but its own pipeline to hide the memory latency behind:
     // one image alone (Model.evaluate's reference flow), the hyper transforms.  Such a launch runs the deep-ring instance
     // (six stages in flight per workgroup instead of two) where the plan allows direct-to-LDS staging at all.  Same bits.
-    s.deep = !fused && !s.sk && p->dma != 0 && p->vec && !p->rowpack && !pro && !p->bf3 && gg_resident_blocks_deep(v) > 0 &&
-             tiles * ksplit <= (int64_t)kDeepBlocksPerCU * gg_num_cus();
+    const bool deep_ok = !fused && !s.sk && p->dma != 0 && p->vec && !p->rowpack && !pro && !p->bf3 &&
+                         tiles * ksplit <= (int64_t)kDeepBlocksPerCU * gg_num_cus();
+    const GGInstance* deep = deep_ok ? gg_find(v, kLoadVec, kStageDeep, kFormPlain) : nullptr;
+    if (deep) s.inst = deep;
     if (s.sk) {
       cost *= (double)resident / workers;
-    } else if (s.deep) {
+    } else if (deep) {
       cost *= std::max(1.0, (double)gg_num_cus() / (double)(tiles * ksplit)) * kDeepCost;
     } else {
       const double rounds = (double)(tiles * ksplit) / resident;
@@ -705,10 +734,11 @@ static Sched schedule(const sntc_conv_plan* p, const Geo& g, int64_t n, bool fus
 #ifdef SNTC_DIAG
     if (getenv("SNTC_SCHED_DBG"))
       fprintf(stderr, "[sched] M=%lld v=%d sk=%d workers=%d blocks=%lld tiles=%lld units=%lld resident=%d deep=%d cost=%.4g (macs %.4g)\n", (long long)M, v,
-              (int)s.sk, s.workers, (long long)s.blocks, (long long)tiles, (long long)units, resident, (int)s.deep, cost, macs);
+              (int)s.sk, s.workers, (long long)s.blocks, (long long)tiles, (long long)units, resident, deep ? 1 : 0, cost, macs);
 #endif
     if (cost < best_cost) { best_cost = cost; best = s; }
   }
+  if (const GGInstance* twin = column_major(p, best)) best.inst = twin;
   return best;
 }
 
@@ -729,7 +759,7 @@ static Sched plan_schedule(const sntc_conv_plan* p, const Geo& g, int n, int h, 
     if (have && c.sk != 0 && !g_stream_k_enabled.load(std::memory_order_relaxed)) have = false;
     if (have) {
       const Sched s = schedule(p, g, n, false, &c);
-      if (s.valid) return s;
+      if (s.inst) return s;
     }
   }
   return schedule(p, g, n, fused);
@@ -737,7 +767,7 @@ static Sched plan_schedule(const sntc_conv_plan* p, const Geo& g, int n, int h, 
 
 static int64_t workspace_floats(const sntc_conv_plan* p, int64_t M, const Sched& s) {
   if (s.sk)      // slabs + one flag per worker
-    return (int64_t)s.workers * (int64_t)(s.variant > kNumVariants ? bf3p_sk_slab_floats(s.variant) : gg_sk_slab_floats(s.variant)) + s.workers;
+    return (int64_t)s.workers * (int64_t)s.inst->slab_floats + s.workers;
   if (s.ksplit <= 1) return 0;
   int64_t cols = 0;
   for (int gi = 0; gi < p->ngroups; ++gi) cols += p->g[gi].Ncol;
@@ -751,20 +781,13 @@ extern "C" int64_t sntc_conv_workspace_bytes(const sntc_conv_plan* p, int n, int
   return 4 * workspace_floats(p, (int64_t)n * g.Qh * g.Qw, plan_schedule(p, g, n, h, w));
 }
 
-// fp32 stream-K unit order of a launch: column tile outermost for single-group plans whose packed weights do not fit an XCD's
-// 4 MB L2, where the twin of the kernel exists (csrc/gather_gemm.hip, COLM)
-static bool column_major(const sntc_conv_plan* p, const Sched& sc, int dma) {
-  return !p->s3 && !p->bf3 && sc.sk && p->ngroups == 1 && p->colm != 0 && gg_colm_available(sc.variant, p->vec, p->d.prologue, dma) &&
-         (p->colm == 1 || (size_t)p->g[0].Ncol * p->g[0].K * sizeof(float) > ((size_t)4 << 20));
-}
-
 extern "C" int sntc_conv_launch_order(const sntc_conv_plan* p, int n, int h, int w, int* column_major_out) {
   if (!p || !column_major_out) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_launch_order: null argument");
   Geo g;
   int rc = geometry(p, h, w, &g);
   if (rc) return rc;
   const Sched s = plan_schedule(p, g, n, h, w);
-  *column_major_out = column_major(p, s, s.deep ? 2 : plan_dma(p) ? 1 : 0) ? 1 : 0;
+  *column_major_out = s.inst && s.inst->form == kFormColm ? 1 : 0;
   return SNTC_OK;
 }
 
@@ -774,7 +797,7 @@ extern "C" int sntc_conv_launch_info(const sntc_conv_plan* p, int n, int h, int 
   int rc = geometry(p, h, w, &g);
   if (rc) return rc;
   const Sched s = plan_schedule(p, g, n, h, w);
-  *variant = s.variant;
+  *variant = s.inst ? s.inst->variant : 0;
   *nblocks = (int)s.blocks;
   return SNTC_OK;
 }
@@ -798,13 +821,12 @@ static int conv_forward_impl(const sntc_conv_plan* p, const sntc_conv_plan* p2, 
     return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_forward: input tensor must be < 2 GiB (32-bit buffer offsets); split the batch");
   if (p2 && M * p2->d.cout >= (1LL << 32)) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_forward_fused: output too large; split the batch");
   const Sched sc = force ? schedule(p, g, n, false, force) : plan_schedule(p, g, n, h, w, p2 != nullptr);
-  if (!sc.valid) return fail(SNTC_ERR_UNSUPPORTED, "sntc_conv_forward: no tile variant for this plan");
+  if (!sc.inst) return fail(SNTC_ERR_UNSUPPORTED, "sntc_conv_forward: no compiled instance for this plan and tile variant");
   const int64_t ws_floats = workspace_floats(p, M, sc);
   if (ws_floats > 0 && (!workspace || workspace_bytes < (size_t)ws_floats * 4))
     return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_forward: this call needs sntc_conv_workspace_bytes() of workspace "
                                     "(split-K slabs / stream-K hand-off)");
-  const int v = sc.variant;
-  const int bm = variant_bm(v), bn = variant_bn(v);
+  const GGInstance& inst = *sc.inst;
   GGArgs a{};
   a.ksplit = sc.ksplit;
   a.slab = static_cast<float*>(workspace);
@@ -815,10 +837,8 @@ static int conv_forward_impl(const sntc_conv_plan* p, const sntc_conv_plan* p2, 
   a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = d.cout;
   a.sA = g.sA; a.tstep = g.tstep; a.offy = g.offy; a.offx = g.offx; a.sO = g.sO;
   a.act = d.act; a.epi = epilogue; a.pro = d.prologue;
-  a.ntm = (int)((M + bm - 1) / bm);
+  a.ntm = (int)((M + inst.bm - 1) / inst.bm);
   a.ngroups = p->ngroups;
-  a.bf3 = p->bf3 ? 1 : 0;
-  a.dma = p2 ? 0 : sc.deep ? 2 : plan_dma(p) ? 1 : 0;
   if (p2) { a.w2f = p2->w2f; a.bias2 = p2->bias; a.Cout2 = p2->d.cout; }
   a.status = gg_status_word();
   if (!a.status) return fail(SNTC_ERR_HIP, "sntc_conv_forward: the device tables of the current device are not initialised");
@@ -827,7 +847,7 @@ static int conv_forward_impl(const sntc_conv_plan* p, const sntc_conv_plan* p2, 
   a.units = sc.units;
   if (sc.sk) {
     a.sk_slab = static_cast<float*>(workspace);
-    a.sk_flags = reinterpret_cast<int*>(a.sk_slab + (size_t)sc.workers * (v > kNumVariants ? bf3p_sk_slab_floats(v) : gg_sk_slab_floats(v)));
+    a.sk_flags = reinterpret_cast<int*>(a.sk_slab + (size_t)sc.workers * inst.slab_floats);
     a.slab = nullptr;
     if (int zrc = zero_async(a.sk_flags, sizeof(int) * sc.workers, (hipStream_t)stream)) return zrc;
   }
@@ -838,7 +858,7 @@ static int conv_forward_impl(const sntc_conv_plan* p, const sntc_conv_plan* p2, 
     GGGroup& G = a.g[gi];
     G.wp = p->g[gi].wp; G.taps = p->g[gi].taps; G.cols = reinterpret_cast<const int*>(p->g[gi].cols);
     G.T = p->g[gi].T; G.K = p->g[gi].K; G.Ncol = p->g[gi].Ncol; G.tw = p->g[gi].tw;
-    G.ntn = (G.Ncol + bn - 1) / bn;
+    G.ntn = (G.Ncol + inst.bn - 1) / inst.bn;
     G.steps = G.K / kStage;
     G.blk0 = nb;
     G.tile0 = tile0;
@@ -852,26 +872,12 @@ static int conv_forward_impl(const sntc_conv_plan* p, const sntc_conv_plan* p2, 
   }
   a.tps = tile0;
   a.ups = (int)unit0;
-  if (p->s3) {
-    // stream-K unit order: strip-major, as the fp32 kernel (every worker's share mixes the phase groups; with the column tile
-    // outermost the last workers of the 13x13/8 synthesis get nothing but 20-stage tiles: 0.55 against 0.45 ms).  The column-major
-    // order stays selectable for the A/B: sntc_conv_plan_set_schedule's stage-path bit ("off") doubles as the switch here
-    a.order = p->dma == 0 ? 0 : 1;
-    // patch staging: the taps of a slab sample the input at unit stride, and every group's patch (tile rows + the tap window's
-    // reach in flattened macro pixels + a zero row) fits the patch buffers; <= 32 taps (the kernel keeps one validity bit per tap
-    // and row)
-    bool halo = !p->no_halo && g.sA == 1;
-    for (int gi = 0; halo && gi < p->ngroups; ++gi) {
-      const int th = p->g[gi].T / p->g[gi].tw;
-      halo = p->g[gi].T <= 32 && bm + (th - 1) * g.Qw + p->g[gi].tw - 1 + (p->g[gi].T > 1 ? 1 : 0) <= bf3p_patch_rows_max();
-    }
-    a.halo = halo ? 1 : 0;
-    return bf3p_launch(v, a, sc.sk ? sc.workers : nb, (hipStream_t)stream);
-  }
-  // stream-K unit order of the fp32 kernel: column tile outermost (GGArgs::order == 0) for single-group plans whose packed
-  // weights do not fit an XCD's 4 MB L2 -- the 3x3 hyper-synthesis layer (11 MB): HBM-side reads of the launch 1667 -> 857 MB
-  a.order = (!p2 && column_major(p, sc, a.dma)) ? 0 : 1;
-  rc = gg_launch(v, p->vec, a, sc.sk ? sc.workers : nb, (hipStream_t)stream);
+  // pre-split stream-K unit order: strip-major, as the fp32 kernel (every worker's share mixes the phase groups; with the column
+  // tile outermost the last workers of the 13x13/8 synthesis get nothing but 20-stage tiles: 0.55 against 0.45 ms).  The
+  // column-major order stays selectable for the A/B: sntc_conv_plan_set_schedule's stage-path bit ("off") doubles as the switch
+  // here.  The other mode fields of GGArgs, and the fp32 order, are the instance's (gg_launch).
+  if (p->s3) a.order = p->dma == 0 ? 0 : 1;
+  rc = gg_launch(inst, a, sc.sk ? sc.workers : nb, (hipStream_t)stream);
   if (rc || sc.sk || sc.ksplit <= 1) return rc;
   return gg_reduce_launch(a, (hipStream_t)stream);
 }
@@ -888,16 +894,17 @@ extern "C" int sntc_conv_forward(const sntc_conv_plan* p, const float* x, int n,
 // caller's buffers, for one (n, h, w), and records the winner in the plan.  Split-K factors are not candidates (they are a
 // function of the layer and the per-image geometry only, by contract).
 static void tune_candidates(const sntc_conv_plan* p, const Geo& g, int n, std::vector<std::pair<TuneChoice, Sched>>* out) {
-  const int v0 = p->s3 ? 11 : 1, v1 = p->s3 ? 13 : kNumVariants;
-  for (int v = v0; v <= v1; ++v)
+  for (int v = 1; v <= kMaxVariant; ++v) {
+    if (!base_instance(p, v)) continue;
     for (int sk = 1; sk >= 0; --sk) {
       TuneChoice c;
       c.variant = v;
       c.sk = sk;
       const Sched s = schedule(p, g, n, false, &c);
-      if (!s.valid || s.variant != v || (sk && !s.sk)) continue;
+      if (!s.inst || s.inst->variant != v || (sk && !s.sk)) continue;
       out->push_back({c, s});
     }
+  }
 }
 
 extern "C" int64_t sntc_conv_tune_workspace_bytes(const sntc_conv_plan* p, int n, int h, int w) {
@@ -963,7 +970,7 @@ extern "C" int sntc_conv_plan_set_choice(sntc_conv_plan* p, int n, int h, int w,
   c.variant = variant;
   c.sk = stream_k ? 1 : 0;
   const Sched s = schedule(p, g, n, false, &c);
-  if (!s.valid || s.variant != variant || (stream_k && !s.sk))
+  if (!s.inst || s.inst->variant != variant || (stream_k && !s.sk))
     return fail(SNTC_ERR_UNSUPPORTED, "sntc_conv_plan_set_choice: not a candidate of this plan for this call shape");
   std::lock_guard<std::mutex> lk(p->tune_mu);
   p->tuned[{n, h, w}] = c;

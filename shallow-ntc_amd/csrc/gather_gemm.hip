@@ -1,10 +1,11 @@
-// gather_gemm.hip -- host side of the gather GEMM: the split-K finish kernel, the table of instantiations (defined in
-// gg_inst_*.hip, declared here), residency tables per device, the launch.
+// gather_gemm.hip -- host side of the gather GEMM: the split-K finish kernel, the table of compiled instances (defined in
+// gg_inst_*.hip and bf3_gemm.hip), residency tables per device, the launch.
 #include "gather_gemm_kernel.h"
 
 namespace sntc {
 
-// the instantiations live in their own translation units (gather_gemm_kernel.h, bottom)
+// the instantiations live in their own translation units (gather_gemm_kernel.h, bottom); declared here so that the table
+// below takes their addresses without instantiating them again
 #define SNTC_GG_DECL_VEC(TM, TN, WM, WN) extern template __global__ void gg_kernel<TM, TN, WM, WN, true, false>(const GGArgs);
 #define SNTC_GG_DECL_PRO(TM, TN, WM, WN)                                                   \
   extern template __global__ void gg_kernel<TM, TN, WM, WN, true, true>(const GGArgs);    \
@@ -55,96 +56,63 @@ int gg_reduce_launch(const GGArgs& args, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// variants + launch
+// the instance table
 // ---------------------------------------------------------------------------------------------
-// variant -> (TM, TN, WM, WN): 1..7 one 32-row tile x v column tiles per wave, four waves stacked (128 x 32v);
-// 8: 64 x 64 (2 x 2 waves of 32 x 32); 9: 128 x 128 as 2 x 2 waves of 64 x 64; 10: 256 x 128 as four waves of 64 x 128
-int gg_variant_bm(int v) { return v == 8 ? 64 : v == 10 ? 256 : 128; }
-int gg_variant_bn(int v) { return v == 8 ? 64 : v >= 9 ? 128 : 32 * v; }
-size_t gg_sk_slab_floats(int v) {
-  const int tiles = v == 8 ? 1 : v == 9 ? 4 : v == 10 ? 8 : v;
-  return (size_t)tiles * 16 * 256;
+// One row per compiled instance.  Tile (32 TM WM x 32 TN WN), threads (64 WM WN) and the stream-K hand-off slab (every thread's
+// TM x TN accumulator tiles of 16 floats) follow from the template arguments; the dynamic LDS from the ring the instance stages
+// through, plus the tile's row table.
+static GGInstance row(int v, GGLoad load, GGStage stage, GGForm form, int TM, int TN, int WM, int WN, const void* fn) {
+  GGInstance r{v, load, stage, form, 32 * TM * WM, 32 * TN * WN, 64 * WM * WN, 0, (size_t)TM * TN * 16 * 64 * WM * WN, fn};
+  const size_t rinfo = 2 * r.bm * sizeof(int4);
+  if (form == kFormPresplitHalo)         // the activation patch buffers + the weight ring (three bf16 planes: 96 B per row)
+    r.lds = (size_t)2 * kBf3PatchRounds * 512 * 16 + (size_t)(v == 12 ? kBf3DeepRing : 3) * r.bn * 96 + rinfo;
+  else if (form == kFormBf3 || form == kFormPresplit)    // three slots of (BM + BN) rows of 96 B
+    r.lds = (size_t)3 * (r.bm + r.bn) * 96 + rinfo;
+  else                                   // fp32: three, four (direct-to-LDS) or kDeepRing slots of (BM + BN) rows of 64 B
+    r.lds = (size_t)(stage == kStageDeep ? kDeepRing : stage == kStageDma ? 4 : 3) * (r.bm + r.bn) * kStage * sizeof(float) + rinfo;
+  return r;
 }
 
-static size_t lds_bytes(int v) {
-  return (size_t)3 * (gg_variant_bm(v) + gg_variant_bn(v)) * kStage * sizeof(float) + 2 * gg_variant_bm(v) * sizeof(int4);
+#define GG(v, load, stage, form, TM, TN, WM, WN, ...) \
+  row(v, load, stage, form, TM, TN, WM, WN, reinterpret_cast<const void*>(&gg_kernel<TM, TN, WM, WN, __VA_ARGS__>))
+#define GG_LOADERS(v, TM, TN, WM, WN)                                        \
+  GG(v, kLoadVec, kStageRing, kFormPlain, TM, TN, WM, WN, true, false),      \
+  GG(v, kLoadVecPro, kStageRing, kFormPlain, TM, TN, WM, WN, true, true),    \
+  GG(v, kLoadGather, kStageRing, kFormPlain, TM, TN, WM, WN, false, true)
+#define GG_DMA(v, TM, TN, WM, WN) GG(v, kLoadVec, kStageDma, kFormPlain, TM, TN, WM, WN, true, false, false, true)
+// bf3_kernel<WM = 4, WN = 2, TM = 2, TN, ...>: eight waves of 64 x 32 TN (bf3_gemm.hip)
+#define BF3P(v, TN, form) row(v, kLoadVec, kStageDma, form, 2, TN, 4, 2, bf3p_kernel(v, form == kFormPresplitHalo))
+
+static const GGInstance kInstances[] = {
+    GG_LOADERS(1, 1, 1, 4, 1), GG_LOADERS(2, 1, 2, 4, 1), GG_LOADERS(3, 1, 3, 4, 1), GG_LOADERS(4, 1, 4, 4, 1), GG_LOADERS(5, 1, 5, 4, 1),
+    GG_LOADERS(6, 1, 6, 4, 1), GG_LOADERS(7, 1, 7, 4, 1), GG_LOADERS(8, 1, 1, 2, 2), GG_LOADERS(9, 2, 2, 2, 2), GG_LOADERS(10, 2, 4, 4, 1),
+    GG_DMA(1, 1, 1, 4, 1), GG_DMA(2, 1, 2, 4, 1), GG_DMA(3, 1, 3, 4, 1), GG_DMA(4, 1, 4, 4, 1), GG_DMA(5, 1, 5, 4, 1),
+    GG_DMA(8, 1, 1, 2, 2), GG_DMA(9, 2, 2, 2, 2),
+    // 8-slot ring (six stages in flight per workgroup) for launches of about one workgroup per CU or fewer, where nothing else
+    // hides the memory latency: the 64 x 64 tile, which is what such launches are cut into
+    GG(8, kLoadVec, kStageDeep, kFormPlain, 1, 1, 2, 2, true, false, false, true, kDeepRing),
+    // the ResidualBlock tail fused behind the 128 x 96 tile (3x3, N = 96 -> 1x1, 96 -> 192)
+    GG(3, kLoadVec, kStageRing, kFormFuse2, 1, 3, 4, 1, true, false, false, false, 0, true),
+    // the column-tile-outermost twin of the 128 x 128 stream-K instance (GGArgs::order == 0; single-group plans)
+    GG(9, kLoadVec, kStageRing, kFormColm, 2, 2, 2, 2, true, false, false, false, 0, false, true),
+    GG(2, kLoadVec, kStageRing, kFormBf3, 1, 2, 4, 1, true, false, true),
+    GG(4, kLoadVec, kStageRing, kFormBf3, 1, 4, 4, 1, true, false, true),
+    BF3P(11, 4, kFormPresplit), BF3P(11, 4, kFormPresplitHalo), BF3P(12, 2, kFormPresplit), BF3P(12, 2, kFormPresplitHalo),
+    BF3P(13, 3, kFormPresplit), BF3P(13, 3, kFormPresplitHalo),
+};
+#undef GG
+#undef GG_LOADERS
+#undef GG_DMA
+#undef BF3P
+constexpr int kNumInstances = sizeof(kInstances) / sizeof(kInstances[0]);
+
+const GGInstance* gg_find(int variant, GGLoad load, GGStage stage, GGForm form) {
+  for (const GGInstance& r : kInstances)
+    if (r.variant == variant && r.load == load && r.stage == stage && r.form == form) return &r;
+  return nullptr;
 }
 
-template <int TM, int TN, int WM, int WN>
-static const void* kernel_ptr(bool vec, bool pro) {
-  if (vec && !pro) return reinterpret_cast<const void*>(&gg_kernel<TM, TN, WM, WN, true, false>);
-  if (vec) return reinterpret_cast<const void*>(&gg_kernel<TM, TN, WM, WN, true, true>);
-  return reinterpret_cast<const void*>(&gg_kernel<TM, TN, WM, WN, false, true>);
-}
-
-static const void* variant_kernel_dma(int v) {
-  switch (v) {
-    case 1: return reinterpret_cast<const void*>(&gg_kernel<1, 1, 4, 1, true, false, false, true>);
-    case 2: return reinterpret_cast<const void*>(&gg_kernel<1, 2, 4, 1, true, false, false, true>);
-    case 3: return reinterpret_cast<const void*>(&gg_kernel<1, 3, 4, 1, true, false, false, true>);
-    case 4: return reinterpret_cast<const void*>(&gg_kernel<1, 4, 4, 1, true, false, false, true>);
-    case 5: return reinterpret_cast<const void*>(&gg_kernel<1, 5, 4, 1, true, false, false, true>);
-    case 8: return reinterpret_cast<const void*>(&gg_kernel<1, 1, 2, 2, true, false, false, true>);
-    case 9: return reinterpret_cast<const void*>(&gg_kernel<2, 2, 2, 2, true, false, false, true>);
-    default: return nullptr;
-  }
-}
-
-static size_t lds_bytes_dma(int v) {
-  return (size_t)4 * (gg_variant_bm(v) + gg_variant_bn(v)) * kStage * sizeof(float) + 2 * gg_variant_bm(v) * sizeof(int4);
-}
-
-// 8-slot ring (six stages in flight per workgroup) for launches of about one workgroup per CU or fewer, where nothing else
-// hides the memory latency: the 64 x 64 tile, which is what such launches are cut into
-static const void* variant_kernel_deep(int v) {
-  switch (v) {
-    case 8: return reinterpret_cast<const void*>(&gg_kernel<1, 1, 2, 2, true, false, false, true, kDeepRing>);
-    default: return nullptr;
-  }
-}
-
-static size_t lds_bytes_deep(int v) {
-  return (size_t)kDeepRing * (gg_variant_bm(v) + gg_variant_bn(v)) * kStage * sizeof(float) + 2 * gg_variant_bm(v) * sizeof(int4);
-}
-
-// the ResidualBlock tail fused behind the 128 x 96 tile (3x3, N = 96 -> 1x1, 96 -> 192)
-static const void* kernel_fused() {
-  return reinterpret_cast<const void*>(&gg_kernel<1, 3, 4, 1, true, false, false, false, 0, true>);
-}
-
-// the column-tile-outermost twin of the 128 x 128 stream-K instance (GGArgs::order == 0; single-group plans)
-static const void* kernel_colm() {
-  return reinterpret_cast<const void*>(&gg_kernel<2, 2, 2, 2, true, false, false, false, 0, false, true>);
-}
-static bool colm_shape(int variant, bool vec, int pro, int dma) { return variant == 9 && vec && pro == SNTC_PRO_NONE && dma == 0; }
-
-static const void* variant_kernel_bf3(int v) {
-  switch (v) {
-    case 2: return reinterpret_cast<const void*>(&gg_kernel<1, 2, 4, 1, true, false, true>);
-    case 4: return reinterpret_cast<const void*>(&gg_kernel<1, 4, 4, 1, true, false, true>);
-    default: return nullptr;
-  }
-}
-
-static size_t lds_bytes_bf3(int v) {
-  return (size_t)3 * (gg_variant_bm(v) + gg_variant_bn(v)) * 96 + 2 * gg_variant_bm(v) * sizeof(int4);
-}
-
-static const void* variant_kernel(int v, bool vec, bool pro) {
-  switch (v) {
-    case 1: return kernel_ptr<1, 1, 4, 1>(vec, pro);
-    case 2: return kernel_ptr<1, 2, 4, 1>(vec, pro);
-    case 3: return kernel_ptr<1, 3, 4, 1>(vec, pro);
-    case 4: return kernel_ptr<1, 4, 4, 1>(vec, pro);
-    case 5: return kernel_ptr<1, 5, 4, 1>(vec, pro);
-    case 6: return kernel_ptr<1, 6, 4, 1>(vec, pro);
-    case 7: return kernel_ptr<1, 7, 4, 1>(vec, pro);
-    case 8: return kernel_ptr<1, 1, 2, 2>(vec, pro);
-    case 9: return kernel_ptr<2, 2, 2, 2>(vec, pro);
-    case 10: return kernel_ptr<2, 4, 4, 1>(vec, pro);
-    default: return nullptr;
-  }
-}
+static bool presplit(const GGInstance& r) { return r.form == kFormPresplit || r.form == kFormPresplitHalo; }
 
 // Residency tables, one per device, filled once per process (std::call_once): every thread and every plan sees the same
 // schedule whatever thread created the plan, and switching devices costs a table lookup.
@@ -153,12 +121,7 @@ struct DeviceTables {
   std::once_flag once;
   int rc = SNTC_OK;
   int num_cus = 0;
-  int resident[kNumVariants + 1][3] = {};      // per (variant, {vec, vec+pro, gather}) workgroups per device
-  int resident_bf3[kNumVariants + 1] = {};
-  int resident_dma[kNumVariants + 1] = {};
-  int resident_deep[kNumVariants + 1] = {};
-  int resident_fused = 0;
-  bool colm_ok = false;                        // the column-major twin of variant 9 is as resident as variant 9 itself
+  int resident[kNumInstances] = {};            // workgroups per device, by row of kInstances
   int* status = nullptr;                       // sticky status word (device memory)
 };
 static DeviceTables g_dev[kMaxDevices];
@@ -167,53 +130,19 @@ static int fill_tables(DeviceTables& T, int dev) {
   hipDeviceProp_t prop;
   SNTC_HIP(hipGetDeviceProperties(&prop, dev));
   T.num_cus = prop.multiProcessorCount;
-  for (int v = 1; v <= kNumVariants; ++v) {
-    for (int k = 0; k < 3; ++k) {
-      const void* fn = variant_kernel(v, k < 2, k >= 1);
-      SNTC_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(v)));
-      int per_cu = 0;
-      SNTC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds_bytes(v)));
-      // the API can answer one workgroup per CU high near an SGPR allocation edge (MI355X_MICROARCH.md, Residency):
-      // stream-K needs every worker resident, so stay at or below 8 and keep the LDS bound exact
-      per_cu = std::max(1, std::min({per_cu, 8, (int)(163840 / lds_bytes(v))}));
-      T.resident[v][k] = per_cu * T.num_cus;
+  for (int i = 0; i < kNumInstances; ++i) {
+    const GGInstance& r = kInstances[i];
+    SNTC_HIP(hipFuncSetAttribute(r.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds));
+    if (presplit(r)) {                         // one 512-thread workgroup per CU, by construction
+      T.resident[i] = T.num_cus;
+      continue;
     }
-  }
-  for (int v : {1, 2, 3, 4, 5, 8, 9}) {
-    const void* fn = variant_kernel_dma(v);
-    SNTC_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes_dma(v)));
     int per_cu = 0;
-    SNTC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds_bytes_dma(v)));
-    T.resident_dma[v] = std::max(1, std::min({per_cu, 8, (int)(163840 / lds_bytes_dma(v))})) * T.num_cus;
-  }
-  for (int v : {8}) {
-    const void* fn = variant_kernel_deep(v);
-    SNTC_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes_deep(v)));
-    int per_cu = 0;
-    SNTC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds_bytes_deep(v)));
-    T.resident_deep[v] = std::max(1, std::min({per_cu, 8, (int)(163840 / lds_bytes_deep(v))})) * T.num_cus;
-  }
-  {
-    const void* fn = kernel_fused();
-    SNTC_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(3)));
-    int per_cu = 0;
-    SNTC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds_bytes(3)));
-    T.resident_fused = std::max(1, std::min({per_cu, 8, (int)(163840 / lds_bytes(3))})) * T.num_cus;
-  }
-  {
-    const void* fn = kernel_colm();
-    SNTC_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(9)));
-    int per_cu = 0;
-    SNTC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds_bytes(9)));
-    // stream-K sizes its worker count from the strip-major instance's residency: the twin must hold as many
-    T.colm_ok = std::max(1, std::min({per_cu, 8, (int)(163840 / lds_bytes(9))})) * T.num_cus >= T.resident[9][0];
-  }
-  for (int v : {2, 4}) {
-    const void* fn = variant_kernel_bf3(v);
-    SNTC_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes_bf3(v)));
-    int per_cu = 0;
-    SNTC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds_bytes_bf3(v)));
-    T.resident_bf3[v] = std::max(1, std::min({per_cu, 8, (int)(163840 / lds_bytes_bf3(v))})) * T.num_cus;
+    SNTC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r.fn, r.threads, r.lds));
+    // the API can answer one workgroup per CU high near an SGPR allocation edge (MI355X_MICROARCH.md, Residency):
+    // stream-K needs every worker resident, so stay at or below 8 and keep the LDS bound exact
+    per_cu = std::max(1, std::min({per_cu, 8, (int)(163840 / r.lds)}));
+    T.resident[i] = per_cu * T.num_cus;
   }
   SNTC_HIP(hipMalloc(&T.status, 2 * sizeof(int)));      // [0] the sticky word, [1] where sntc_conv_status's exchange returns it
   SNTC_HIP(hipMemset(T.status, 0, 2 * sizeof(int)));
@@ -237,20 +166,9 @@ int gg_init() {
   return T.rc;
 }
 
-int gg_resident_blocks(int variant, bool vec, bool pro) {
+int gg_resident(const GGInstance& inst) {
   const DeviceTables* T = current_tables();
-  if (variant < 1 || variant > kNumVariants || !T) return 0;
-  return T->resident[variant][!vec ? 2 : (pro ? 1 : 0)];
-}
-
-int gg_resident_blocks_dma(int variant) {
-  const DeviceTables* T = current_tables();
-  return variant >= 1 && variant <= kNumVariants && variant_kernel_dma(variant) && T ? T->resident_dma[variant] : 0;
-}
-
-int gg_resident_blocks_deep(int variant) {
-  const DeviceTables* T = current_tables();
-  return variant >= 1 && variant <= kNumVariants && variant_kernel_deep(variant) && T ? T->resident_deep[variant] : 0;
+  return T ? T->resident[&inst - kInstances] : 0;
 }
 
 int gg_num_cus() {
@@ -263,43 +181,19 @@ int* gg_status_word() {
   return T ? T->status : nullptr;
 }
 
-int gg_resident_blocks_fused() {
-  const DeviceTables* T = current_tables();
-  return T ? T->resident_fused : 0;
-}
-
-// the column-major stream-K twin exists for this launch shape on the current device
-bool gg_colm_available(int variant, bool vec, int pro, int dma) {
-  const DeviceTables* T = current_tables();
-  return T && T->colm_ok && colm_shape(variant, vec, pro, dma);
-}
-
-int gg_resident_blocks_bf3(int variant) {
-  const DeviceTables* T = current_tables();
-  return (variant == 2 || variant == 4) && T ? T->resident_bf3[variant] : 0;
-}
-
-int gg_launch(int variant, bool vec, const GGArgs& args, int nblocks, hipStream_t stream) {
-  const bool pro = args.pro != SNTC_PRO_NONE;
-  const bool deep = args.dma == 2 && vec && !pro && !args.bf3 && variant_kernel_deep(variant);
-  const bool dma = !deep && args.dma && vec && !pro && !args.bf3 && variant_kernel_dma(variant);
-  const bool fused = args.w2f != nullptr;
-  if (fused && (variant != 3 || !vec || pro || args.bf3 || args.ksplit != 1))
-    return fail(SNTC_ERR_UNSUPPORTED, "fused ResidualBlock tail: 128 x 96 vector instance, no prologue, no split-K");
-  const bool colm = !fused && !args.bf3 && args.sk && args.order == 0 && args.ngroups == 1 && colm_shape(variant, vec, args.pro, args.dma);
-  if (!fused && !args.bf3 && args.sk && args.order == 0 && !colm)
-    return fail(SNTC_ERR_UNSUPPORTED, "column-major stream-K order: single-group plans on the 128 x 128 register-staged vector instance only");
-  const void* fn = fused ? kernel_fused() : args.bf3 ? variant_kernel_bf3(variant) : deep ? variant_kernel_deep(variant)
-                   : dma ? variant_kernel_dma(variant) : colm ? kernel_colm() : variant_kernel(variant, vec, pro || !vec);
-  if (!fn) return fail(SNTC_ERR_UNSUPPORTED, "unknown gather-GEMM tile variant");
-  if (args.bf3 && (pro || !vec)) return fail(SNTC_ERR_UNSUPPORTED, "bf16 x 3 mode: vector path without prologue only");
+// The launch of one resolved instance: the mode fields of GGArgs are the instance's (the pre-split kernels take GGArgs::order
+// from the caller: there it is the plan's A/B switch of the unit order, not an instance).
+int gg_launch(const GGInstance& inst, const GGArgs& args, int nblocks, hipStream_t stream) {
   GGArgs a = args;
+  a.dma = inst.stage;
+  a.bf3 = inst.form == kFormBf3 || presplit(inst) ? 1 : 0;
+  a.halo = inst.form == kFormPresplitHalo ? 1 : 0;
+  if (!presplit(inst)) a.order = inst.form == kFormColm ? 0 : 1;
 #ifdef SNTC_DIAG
   if (const char* e = getenv("SNTC_GG_DBG")) a.dbg = atoi(e);   // diagnostic builds only (make DIAG=1): results are WRONG with it
 #endif
   void* params[] = {&a};
-  hipError_t e = hipLaunchKernel(fn, dim3(nblocks), dim3(256), params,
-                                 args.bf3 ? lds_bytes_bf3(variant) : deep ? lds_bytes_deep(variant) : dma ? lds_bytes_dma(variant) : lds_bytes(variant), stream);
+  hipError_t e = hipLaunchKernel(inst.fn, dim3(nblocks), dim3(inst.threads), params, inst.lds, stream);
   if (e != hipSuccess) return hip_fail(e, "gather-GEMM launch");
   return SNTC_OK;
 }

@@ -88,7 +88,7 @@ struct GGArgs {
   int dma;             // 1: direct-to-LDS staging (buffer_load ... lds, four ring slots) where the instantiation exists
   int bf3;             // 1: bf16 x 3 split-precision experiment (weights packed as three bf16 planes)
   int halo;            // bf3_gemm.hip: 1 = patch staging (one activation patch per channel slab shared by its taps); needs sA == 1
-                       // and every group's patch within bf3p_patch_rows_max()
+                       // and every group's patch within bf3p_patch_rows_max() (set by gg_launch from the instance, as dma and bf3)
   int order;           // stream-K unit order: 1 strip-major (default), 0 column tile outermost (bf3_gemm.hip: A/B switch;
                        // gather_gemm.hip: the COLM twin of the 128 x 128 instance, single-group plans whose weights exceed an XCD's L2)
   int dbg;             // -DSNTC_DIAG builds only (SNTC_GG_DBG): 1 skip global loads, 2 skip LDS writes, 4 skip barriers,
@@ -98,33 +98,40 @@ struct GGArgs {
   GGGroup g[kMaxGroups];
 };
 
-// variant ids (BM x BN):  1..7 -> 128 x 32*v ;  8 -> 64 x 64 ;  9 -> 128 x 128 (64 x 64 per wave) ;  10 -> 256 x 128
-constexpr int kNumVariants = 10;
+// Tile variant ids (BM x BN): 1..7 -> 128 x 32*v ; 8 -> 64 x 64 ; 9 -> 128 x 128 (64 x 64 per wave) ; 10 -> 256 x 128 (fp32,
+// gg_kernel); 11 -> 256 x 256, 12 -> 256 x 128, 13 -> 256 x 192 (pre-split bf16 x 3, bf3_kernel in bf3_gemm.hip)
+constexpr int kNumVariants = 10;   // fp32 variants
+constexpr int kMaxVariant = 13;
 constexpr int kStage = 16;         // K depth of one pipeline stage
-int gg_variant_bm(int v);
-int gg_variant_bn(int v);
-int gg_launch(int variant, bool vec, const GGArgs& args, int nblocks, hipStream_t stream);
-int gg_reduce_launch(const GGArgs& args, hipStream_t stream);
-int gg_init();   // sets the dynamic-LDS attribute on every instantiation (idempotent), measures occupancy
-int gg_resident_blocks(int variant, bool vec, bool pro);   // workgroups of this instantiation the device keeps resident
-int gg_resident_blocks_deep(int variant);                   // same for the deep-ring (8-slot) direct-to-LDS instances; 0 if none
-int gg_num_cus();
-int* gg_status_word();                                      // device pointer of the current device's sticky status word
-int gg_resident_blocks_dma(int variant);                    // same for the direct-to-LDS instantiations
-int gg_resident_blocks_fused();
-bool gg_colm_available(int variant, bool vec, int pro, int dma);                             // the FUSE2 instance (variant 3)
-int gg_resident_blocks_bf3(int variant);                    // same for the bf16 x 3 instantiations (variants 2 and 4)
-size_t gg_sk_slab_floats(int variant);                     // per-worker accumulator slab of the stream-K hand-off
 
-// ---- pre-split bf16 x 3 gather GEMM (bf3_gemm.hip): variants 11 (256 x 256) and 12 (256 x 128), 512 threads, one workgroup per CU
+// One compiled gather-GEMM instance (gather_gemm.hip holds the table).  schedule() in conv_plan.hip resolves a
+// launch to one row; residency, tile shape, slab size, LDS and the GGArgs mode fields all come from that row.
+enum GGLoad { kLoadVec, kLoadVecPro, kLoadGather };   // 16-B vector loads, the same with a prologue, dword gather (Cin % 16 != 0)
+enum GGStage { kStageRing, kStageDma, kStageDeep };   // register-staged ring, direct-to-LDS, deep direct-to-LDS ring (= GGArgs::dma)
+enum GGForm { kFormPlain, kFormFuse2, kFormColm, kFormBf3, kFormPresplit, kFormPresplitHalo };
+struct GGInstance {
+  int variant;
+  GGLoad load;
+  GGStage stage;
+  GGForm form;         // FUSE2: fused ResidualBlock tail; COLM: column-major stream-K twin; in-loop bf16 x 3; pre-split (patch staging)
+  int bm, bn, threads;
+  size_t lds;          // dynamic LDS bytes
+  size_t slab_floats;  // stream-K: accumulator slab of one worker's hand-off
+  const void* fn;
+};
+const GGInstance* gg_find(int variant, GGLoad load, GGStage stage, GGForm form);   // nullptr: no such instance is compiled
+int gg_init();   // fills the current device's residency table once (sets every instance's dynamic-LDS attribute)
+int gg_resident(const GGInstance& inst);    // workgroups of the instance the current device keeps resident
+int gg_num_cus();
+int* gg_status_word();                      // device pointer of the current device's sticky status word
+int gg_launch(const GGInstance& inst, const GGArgs& args, int nblocks, hipStream_t stream);
+int gg_reduce_launch(const GGArgs& args, hipStream_t stream);
+
+// ---- pre-split bf16 x 3 gather GEMM (bf3_gemm.hip): 512 threads, one workgroup per CU
 constexpr int kBf3PatchRounds = 5;     // patch staging: at most 5 rounds of 512 16-B chunks = 426 rows of 96 B
 constexpr int kBf3DeepRing = 3;        // weight ring slots of the patch-staging 256 x 128 instance (fragments double-buffered)
 int bf3p_patch_rows_max();
-int bf3p_variant_bm(int v);
-int bf3p_variant_bn(int v);
-size_t bf3p_sk_slab_floats(int v);
-int bf3p_init();
-int bf3p_launch(int variant, const GGArgs& args, int nblocks, hipStream_t stream);
+const void* bf3p_kernel(int variant, bool halo);
 
 // ---- deep-factorized prior (entropy.hip, sga.hip) ----
 constexpr int kMaxW = 4;   // max hidden width

@@ -6,14 +6,14 @@ tile, stream-K, split-K) and the stream-K unit order are speed choices only: eve
 chains.  So each forced choice must (a) meet the float64 bar of test_conv_family_fuzz and (b) give the bits of the heuristic's
 choice on the same plan and input (torch.equal) -- the invariant ops.import_tuning and bench.py's tuning file rely on.
 
-How each instance is reached (csrc/gather_gemm.hip, gg_launch):
+How each instance is reached (csrc/conv_plan.hip, schedule() resolves a launch to one row of csrc/gather_gemm.hip's instance table):
   * vector loader, no prologue: Cin % 16 == 0, SNTC_PRO_NONE, register staging (dma=False or the default);
   * vector loader with prologue: Cin % 16 == 0, SNTC_PRO_ABS / SNTC_PRO_SQUARE;
   * dword gather (always with the prologue template argument): Cin % 16 != 0, any prologue;
   * direct-to-LDS (DMA): dma=True on a vector plan without prologue, variants 1..5, 8, 9; variants 6, 7, 10 have no such
     instance and fall back to register staging (same bits);
   * deep ring: variant 8, vector, no prologue, a static launch of at most two workgroups per CU, stage path not forced off
-    (conv_plan.hip, schedule(): Sched::deep) -- every small forced-variant-8 launch below; dma=False turns it off;
+    (schedule()'s deep rule) -- every small forced-variant-8 launch below; dma=False turns it off;
   * COLM: stream-K on variant 9, vector, no prologue, register staging, one phase group, colm=True;
   * FUSE2: ConvPlan.fused (3x3 96 -> 96 + 1x1 96 -> 192);
   * bf16 x 3: bf16x3=True plans, variants 2 and 4 only (any other forced variant has no instance: SntcError).
