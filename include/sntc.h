@@ -462,6 +462,23 @@ int sntc_rans_decode(const uint16_t* payload, const int64_t* offsets, const uint
                      int64_t elems_per_image, int segments, int lanes, const uint16_t* cdf, const uint32_t* meta, int ntables,
                      int total_entries, const uint32_t* dec, const uint16_t* lut, const uint32_t* lut_meta, int lut_entries,
                      int32_t* values, int32_t* bad_streams, void* stream);
+/* The same coder for ONE latent whose table is its channel (the factorized-prior model, reference factorized/models.py:101-124:
+ *   one deep-factorized density per channel), straight from / to the float latents: no table-id tensor, no int32 copy.
+ *   y / y_hat float [nimages][elems_per_image], flat NHWC; the table of element e of an image is e % channels, the table set has
+ *   `channels` tables, elems_per_image % channels == 0 (checked).  The encoder codes symbol = (int)rintf(y[e]) (round half to
+ *   even, as sntc_round_to_int) and, where y_hat is not NULL, writes (float)symbol there; the decoder writes (float)value.
+ *   Streams, scratch, len_words, offsets, cap_words, segments, lanes, bad_streams: as above, and the words of a stream are those
+ *   sntc_rans_encode emits for the same integers with sntc_channel_table_ids -- either decoder reads either encoder's streams.
+ *   dec / lut / lut_meta: as sntc_rans_decode (all three or none); these kernels keep no id ring in LDS, so every lut_entries
+ *   within sntc_rans_lut_budget() fits, and a little more.  Tables too wide for a CU's LDS are read from global memory.
+ *   A value outside [-32768, 32767] is coded clamped (an escaped value travels in 16 bits); y_hat of the encoder is not. */
+int sntc_rans_encode_channels(const float* y, int nimages, int64_t elems_per_image, int channels, int segments, int lanes,
+                              const uint16_t* cdf, const uint32_t* meta, int total_entries, int64_t cap_words, uint16_t* scratch,
+                              int32_t* len_words, float* y_hat, void* stream);
+int sntc_rans_decode_channels(const uint16_t* payload, const int64_t* offsets, int nimages, int64_t elems_per_image, int channels,
+                              int segments, int lanes, const uint16_t* cdf, const uint32_t* meta, int total_entries,
+                              const uint32_t* dec, const uint16_t* lut, const uint32_t* lut_meta, int lut_entries, float* y_hat,
+                              int32_t* bad_streams, void* stream);
 /* table id of every y element = round(clamp(exp(raw), 0, 63)), raw = hyper[..., c:]; of every z element = channel */
 int sntc_scale_table_ids(const float* hyper, int64_t npix, int c, uint16_t* table_ids, void* stream);
 /* table id = channel (deep-factorized prior: one table per channel). */

@@ -19,62 +19,13 @@
 // uint16 (cdf[n] = 65536 implicit) and live in LDS next to a packed (offset, n, vmin) descriptor per table.
 #include <algorithm>
 #include <type_traits>
-#include "sntc_internal.h"
+#include "rans_common.h"
 
 namespace sntc {
 
-struct RansTables {
-  const unsigned short* cdf;   // concatenated; table t: cdf[off .. off + n), cdf of symbol n (= 65536) implicit
-  const uint2* meta;           // per table: x = off, y = (n << 16) | (vmin & 0xffff); symbol n-1 is ESCAPE
-  int ntables;
-  int total;                   // entries in cdf
-};
-
-// The decoder's own view of the same tables (optional: sntc_rans_decode's dec / lut arguments, built by the host from cdf):
-//   dec  entry s of table t, at dec[off_t + 3 t + s] = (cdf[s] << 16) | (freq[s] - 1), followed by three 0xffffffff -- ONE read
-//        gives a symbol's (start, frequency), and with key = (slot << 16) | 0xfffe, "key >= entry" is "slot >= cdf[s]" for every
-//        real entry (freq - 1 <= 0xfffe: a table has >= 2 symbols) and false for the sentinels;
-//   lut  per table a START TABLE of 2^bits entries, lut[lut_off + (slot >> (16 - bits))] = the largest symbol whose cdf is <= the
-//        first slot of that bucket: the search starts there.  lmeta[t] = (lut_off << 5) | bits.
-struct RansDecTables {
-  const unsigned* dec;
-  const unsigned short* lut;
-  const uint2* meta;           // RansTables::meta
-  const unsigned* lmeta;
-  int ntables;
-  int dec_total;               // entries in dec: total + 3 * ntables, padded to a multiple of 4
-  int lut_total;               // entries in lut, padded to a multiple of 8
-};
-
-// Staging.  A wave that codes one stream has nobody to hide memory latency behind, so nothing in the coding loops
-// touches global memory for input: table ids (and values / stream words) are fetched a CHUNK of 16 steps ahead into
-// registers and dropped into LDS rings when the chunk ends; the loops read LDS only, one to two steps ahead of use.
-constexpr int kChunk = 16;                        // steps per staging chunk (1024 elements)
-constexpr int kWordRing = 4096;                   // decoder: stream words resident in LDS (2 x the most a chunk can eat)
-constexpr int kWordRegs = 2 * kChunk;             // decoder: words one lane fetches per chunk
 constexpr int kStagingBytes = 2 * kChunk * 64 * 2 + 2 * kChunk * 64 * 4;   // encoder: id + value rings; decoder: id + word rings
 static_assert(2 * kChunk * 64 * 2 + kWordRing * 2 <= kStagingBytes, "decoder rings must fit the staging area");
-constexpr int kRansLdsLimit = 150 * 1024 - kStagingBytes;
-constexpr unsigned short kNoTable = 0xffffu;      // ring entry of a lane with no element in that step
-
-template <bool LDS>
-__device__ __forceinline__ void rans_stage_tables(const RansTables& T, unsigned char* smem, const uint2*& meta,
-                                                  const unsigned short*& cdf) {
-  if (LDS) {
-    uint2* m = reinterpret_cast<uint2*>(smem);
-    unsigned short* c = reinterpret_cast<unsigned short*>(smem + (size_t)T.ntables * sizeof(uint2));
-    for (int i = threadIdx.x; i < T.ntables; i += blockDim.x) m[i] = T.meta[i];
-    const unsigned* src = reinterpret_cast<const unsigned*>(T.cdf);   // host pads the table to an even count
-    unsigned* dst = reinterpret_cast<unsigned*>(c);
-    for (int i = threadIdx.x; i < (T.total + 1) / 2; i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
-    meta = m;
-    cdf = c;
-  } else {
-    meta = T.meta;
-    cdf = T.cdf;
-  }
-}
+constexpr int kRansLdsLimit = kRansLdsTotal - kStagingBytes;
 
 // one wave per stream s = (image b, segment sg): elements [b E + sg Eseg, min((b + 1) E, b E + (sg + 1) Eseg))
 template <bool LDS>
@@ -519,31 +470,22 @@ static int blocks_for(long long total) {
   return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
 
-static long long segment_elems(long long elems, int segments) {
-  const long long per = (elems + segments - 1) / segments;
-  return (per + 63) / 64 * 64;
-}
-
-static int table_bytes(int ntables, int total) { return ntables * (int)sizeof(uint2) + ((total + 1) / 2) * 4; }
-
 extern "C" int64_t sntc_rans_cap_words(int64_t elems_per_image, int segments) {
   if (elems_per_image < 1 || segments < 1) return -1;
-  return 2 * segment_elems(elems_per_image, segments) + 128;
+  return 2 * rans_segment_elems(elems_per_image, segments) + 128;
 }
-
-static bool lanes_ok(int lanes) { return lanes == 8 || lanes == 16 || lanes == 32 || lanes == 64; }
 
 extern "C" int sntc_rans_encode(const int32_t* values, const uint16_t* table_ids, int nimages, int64_t elems_per_image,
                                 int segments, int lanes, const uint16_t* cdf, const uint32_t* meta, int ntables, int total_entries,
                                 int64_t cap_words, uint16_t* scratch, int32_t* len_words, void* stream) {
   if (!values || !table_ids || !cdf || !meta || !scratch || !len_words)
     return fail(SNTC_ERR_BAD_SHAPE, "sntc_rans_encode: null argument");
-  if (nimages < 1 || elems_per_image < 1 || segments < 1 || !lanes_ok(lanes) || ntables < 1 || total_entries < 1 ||
+  if (nimages < 1 || elems_per_image < 1 || segments < 1 || !rans_lanes_ok(lanes) || ntables < 1 || total_entries < 1 ||
       cap_words < sntc_rans_cap_words(elems_per_image, segments) || cap_words > 0x3fffffff)
     return fail(SNTC_ERR_BAD_SHAPE, "sntc_rans_encode: bad sizes (cap_words must be >= sntc_rans_cap_words())");
   const RansTables T{cdf, reinterpret_cast<const uint2*>(meta), ntables, total_entries};
-  const long long eseg = segment_elems(elems_per_image, segments);
-  const int ns = nimages * segments, tb = table_bytes(ntables, total_entries), lds = kStagingBytes + tb;
+  const long long eseg = rans_segment_elems(elems_per_image, segments);
+  const int ns = nimages * segments, tb = rans_table_bytes(ntables, total_entries), lds = kStagingBytes + tb;
   hipStream_t s = (hipStream_t)stream;
   if (tb <= kRansLdsLimit) {
     SNTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rans_encode_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -580,13 +522,13 @@ extern "C" int sntc_rans_decode(const uint16_t* payload, const int64_t* offsets,
                                 int lut_entries, int32_t* values, int32_t* bad_streams, void* stream) {
   if (!payload || !offsets || !table_ids || !cdf || !meta || !values || !bad_streams)
     return fail(SNTC_ERR_BAD_SHAPE, "sntc_rans_decode: null argument");
-  if (nimages < 1 || elems_per_image < 1 || segments < 1 || !lanes_ok(lanes) || ntables < 1 || total_entries < 1)
+  if (nimages < 1 || elems_per_image < 1 || segments < 1 || !rans_lanes_ok(lanes) || ntables < 1 || total_entries < 1)
     return fail(SNTC_ERR_BAD_SHAPE, "sntc_rans_decode: bad sizes");
   const bool fast = dec != nullptr;
   if (fast != (lut != nullptr) || fast != (lut_meta != nullptr) ||
       (fast && (lut_entries < ntables || (lut_entries & 7) || lut_entries > sntc_rans_lut_budget(ntables, total_entries))))
     return fail(SNTC_ERR_BAD_SHAPE, "sntc_rans_decode: dec / lut / lut_meta come together, lut_entries a multiple of 8 within sntc_rans_lut_budget()");
-  const long long eseg = segment_elems(elems_per_image, segments);
+  const long long eseg = rans_segment_elems(elems_per_image, segments);
   const int ns = nimages * segments;
   hipStream_t s = (hipStream_t)stream;
   if (int zrc = zero_async(bad_streams, sizeof(int32_t), s)) return zrc;
@@ -601,7 +543,7 @@ extern "C" int sntc_rans_decode(const uint16_t* payload, const int64_t* offsets,
     return SNTC_OK;
   }
   const RansTables T{cdf, reinterpret_cast<const uint2*>(meta), ntables, total_entries};
-  const int tb = table_bytes(ntables, total_entries), lds = kStagingBytes + tb;
+  const int tb = rans_table_bytes(ntables, total_entries), lds = kStagingBytes + tb;
   if (tb <= kRansLdsLimit) {
     SNTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rans_decode_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     hipLaunchKernelGGL(rans_decode_kernel<true>, dim3(ns), dim3(64), lds, s, payload, reinterpret_cast<const long long*>(offsets),

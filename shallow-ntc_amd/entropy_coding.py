@@ -16,6 +16,15 @@ Wire format v3 (little endian): b"SNTC" u16 version (low byte 3; high byte = ari
   + the interleaved 16-bit words (csrc/rans.hip).
 The decoder rebuilds mu / scale indexes with the same hyper-synthesis kernels (deterministic, batch-invariant), so
 encoder and decoder agree bit for bit.
+
+The factorized-prior model (factorized/models.py) has ONE latent and no hyper-synthesis: ``FactorizedCodec``, wire format v4
+  b"SNTC" u16 version (low byte 4; high byte = the arithmetic tag, as above) | u16 n | u32 H | u32 W | u16 C | u16 h | u16 w |
+  u16 segments | u8 lanes | u8 0 | u32 len_words[n * segments] | payload
+with one table per channel of y (``factorized_tables`` on the model's prior) and the channel-indexed coder of
+csrc/rans_channels.hip, which reads the float latents and writes float y_hat in one launch, without a table-id or int32
+tensor (the decoder always; the encoder where it is the faster side, ``FUSED_CHANNEL_ENCODE``).
+The streams themselves are those of v3 (same words as ``rans_encode`` with ``channel_table_ids``).  A v3 blob is refused by
+a factorized model and a v4 blob by a hyperprior model.
 """
 from __future__ import annotations
 
@@ -33,6 +42,7 @@ PRECISION = 16
 TOTAL = 1 << PRECISION
 MAGIC = b"SNTC"
 VERSION = 3
+VERSION_FACTORIZED = 4                    # FactorizedCodec: one latent, table = channel
 ARITH = {"fp32": 0, "bf16x3": 1}          # Model(precision=...): high byte of the version word
 SCALE_MIN, SCALE_MAX, NUM_SCALES = 0.11, 256.0, 64
 SCALE_FACTOR = (math.log(SCALE_MAX) - math.log(SCALE_MIN)) / (NUM_SCALES - 1.0)
@@ -176,6 +186,12 @@ def _p(t):
 PIPELINE_BLOBS = True           # decompress_many: blobs pipelined largest first (False: round 4's two-phase schedule; same pixels)
 USE_START_TABLES = True         # decoder: its own tables in LDS, DeviceTables.dec / .lut (False: binary search of cdf; same values)
 
+FUSED_CHANNEL_ENCODE = False    # FactorizedCodec's encoder: False = round_to_int + channel_table_ids + rans_encode, True = the one
+                                # launch of sntc_rans_encode_channels.  Same bytes.  On the latents of 18 / 1 images of 512 x 768
+                                # at C = 256 the three launches measured about 1.1 ms, the one launch 1.2 - 1.4 ms, so the faster
+                                # side is called; the decoder's one launch measured 2.5 - 2.6 ms against 3.0 - 3.1 ms for its
+                                # composition and is always used (profiles/factorized_codec.json).
+
 ELEMS_PER_SEGMENT = 1 << 18     # one rANS stream (= one wave of coding parallelism, 256 bytes of flushed lane states) per
                                 # this many latent elements: ~0.008 bit / element of overhead; a Kodak image = 1 z + 2 y streams
 
@@ -255,6 +271,67 @@ def rans_decode(payload, lens_h, table_ids, shape, tables: DeviceTables, segment
         if nbad:
             raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {n * segments} rANS streams did not terminate cleanly")
     return values
+
+
+def rans_encode_channels_launch(y, tables: DeviceTables, segments=None, lanes=None, want_y_hat=False):
+    """``rans_encode_launch`` for float latents ``y`` [n, ..., C] whose table is their channel (``tables``: one per channel):
+    rounded (half to even) and coded in ONE launch, no id tensor.  -> (scratch, lens, y_hat or None); y_hat = the rounded
+    latents as floats when asked for."""
+    if y.dtype != torch.float32 or not y.is_contiguous():
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "rans_encode_channels: y must be a contiguous float32 tensor")
+    n, c = y.shape[0], y.shape[-1]
+    if c != tables.ntables:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"rans_encode_channels: {c} channels, {tables.ntables} tables")
+    E = y.numel() // n
+    segments = _segments(E, segments)
+    lanes = _lanes(-(-E // segments), lanes)
+    cap = int(capi.load().sntc_rans_cap_words(E, segments))
+    dev = y.device
+    ns = n * segments
+    scratch = torch.empty((ns, cap), dtype=torch.int16, device=dev)
+    lens = torch.empty((ns,), dtype=torch.int32, device=dev)
+    y_hat = torch.empty_like(y) if want_y_hat else None
+    capi.call("sntc_rans_encode_channels", _p(y), n, E, c, segments, lanes, _p(tables.cdf), _p(tables.meta), tables.total, cap,
+              _p(scratch), _p(lens), _p(y_hat), ops._stream())
+    return scratch, lens, y_hat
+
+
+def rans_encode_channels(y, tables: DeviceTables, segments=None, lanes=None, want_y_hat=False):
+    """-> (payload, len_words int64[n * segments], y_hat or None): the words of ``rans_encode(round_to_int(y),
+    channel_table_ids(y.shape), ...)``."""
+    scratch, lens, y_hat = rans_encode_channels_launch(y, tables, segments, lanes, want_y_hat)
+    lens_h = lens.cpu().numpy().astype(np.int64)
+    return rans_encode_finish(scratch, lens, lens_h), lens_h, y_hat
+
+
+def rans_decode_channels(payload, lens_h, shape, tables: DeviceTables, segments=None, lanes=None, bad=None, offsets=None):
+    """``rans_decode`` for a latent whose table is its channel -> the values as float32 of ``shape`` [n, ..., C] (what the
+    synthesis consumes).  ``bad`` / ``offsets`` as in ``rans_decode``.  The decoder's start tables are used where
+    ``DeviceTables`` could place them (``tables.dec``); else the binary search of ``cdf``."""
+    n, c = shape[0], shape[-1]
+    if c != tables.ntables:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"rans_decode_channels: {c} channels, {tables.ntables} tables")
+    E = int(np.prod(shape)) // n
+    segments = _segments(E, segments)
+    lanes = _lanes(-(-E // segments), lanes)
+    if len(lens_h) != n * segments:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "stream count does not match the image / segment counts")
+    dev = payload.device
+    if offsets is None:
+        offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(lens_h)]).astype(np.int64)).to(dev)
+    y_hat = torch.empty(tuple(shape), dtype=torch.float32, device=dev)
+    deferred = bad is not None
+    if not deferred:
+        bad = torch.zeros((1,), dtype=torch.int32, device=dev)
+    fast = USE_START_TABLES and tables.dec is not None
+    capi.call("sntc_rans_decode_channels", _p(payload), _p(offsets), n, E, c, segments, lanes, _p(tables.cdf), _p(tables.meta),
+              tables.total, _p(tables.dec if fast else None), _p(tables.lut if fast else None),
+              _p(tables.lut_meta if fast else None), tables.lut_total if fast else 0, _p(y_hat), _p(bad), ops._stream())
+    if not deferred:
+        nbad = int(bad.item())
+        if nbad:
+            raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {n * segments} rANS streams did not terminate cleanly")
+    return y_hat
 
 
 def scale_table_ids(hyper):
@@ -532,3 +609,208 @@ class Codec:
 
     def _side_streams(self, count):
         return ops.side_streams(count, self.m.device)
+
+
+# -- wire format v4: pure host functions (numbers in, numbers out; no device) ---------------------------------------------
+HEAD_V4 = "<HHIIHHHHBB"                   # version | n | H | W | C | h | w | segments | lanes | 0
+MAX_IMAGES, MAX_SIDE = Codec.MAX_IMAGES, Codec.MAX_SIDE
+
+
+def pack_v4(arith, n, H, W, c, h, w, segments, lanes, len_words) -> bytes:
+    """Everything of a v4 blob in front of the payload: magic, header, the streams' lengths in 16-bit words."""
+    len_words = np.asarray(len_words, np.int64)
+    if len(len_words) != n * segments:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "stream count does not match the image / segment counts")
+    return MAGIC + struct.pack(HEAD_V4, VERSION_FACTORIZED | (arith << 8), n, H, W, c, h, w, segments, lanes, 0) + len_words.astype("<u4").tobytes()
+
+
+def parse_v4(blob: bytes, arith, latent_shape):
+    """Header and stream lengths of one v4 blob, checked against the decoding model: ``arith`` its arithmetic tag,
+    ``latent_shape(H, W) -> (C, h, w)`` its latents for an H x W image.  Every dimension is recomputed from (H, W) and compared;
+    segments and lanes are recomputed from the latent size: no header field sizes an allocation.
+    -> dict(n, H, W, c, h, w, segments, lanes, lens int64[n * segments], pos = payload offset, words)."""
+    if blob[:4] != MAGIC:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "not an SNTC bitstream")
+    pos = 4 + struct.calcsize(HEAD_V4)
+    if len(blob) < 6:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+    (word,) = struct.unpack_from("<H", blob, 4)
+    ver, tag = word & 0xff, word >> 8
+    if ver != VERSION_FACTORIZED:
+        raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream version {ver}: a factorized-prior model reads version {VERSION_FACTORIZED}")
+    if tag != arith:
+        names = {v: k for k, v in ARITH.items()}
+        raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream was written by a {names.get(tag, tag)!r} model, this model computes "
+                             f"in {names.get(arith, arith)!r}: the pixels would not be reproduced bit for bit")
+    if len(blob) < pos:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+    _, n, H, W, c, h, w, segments, lanes, zero = struct.unpack_from(HEAD_V4, blob, 4)
+    if not (1 <= n <= MAX_IMAGES and 1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream header: implausible batch / image size n={n} H={H} W={W}")
+    want = tuple(int(v) for v in latent_shape(H, W))
+    if (c, h, w) != want:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream header (C, h, w) = {(c, h, w)} does not match this model's latents "
+                             f"for a {H} x {W} image: {want}")
+    e = h * w * c
+    if segments != _segments(e) or lanes != _lanes(-(-e // segments)) or zero != 0:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream header: segment / lane counts do not match the latent size")
+    ns = n * segments
+    if len(blob) < pos + 4 * ns:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+    lens = np.frombuffer(blob, "<u4", ns, pos).astype(np.int64)
+    pos += 4 * ns
+    words = int(lens.sum())
+    if len(blob) != pos + 2 * words:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+    return dict(n=n, H=H, W=W, c=c, h=h, w=w, segments=segments, lanes=lanes, lens=lens, pos=pos, words=words)
+
+
+class FactorizedCodec:
+    """compress / decompress for a factorized-prior ``Model`` (factorized/models.py): wire format v4, one table per channel of
+    y from the model's deep-factorized prior, coded by the channel-indexed kernels (csrc/rans_channels.hip) straight from the
+    analysis output and straight into the synthesis input.  ``decompress(compress(x))`` equals
+    ``model.decode(model.encode(x)[0], None, (H, W))`` bit for bit.
+
+    Known limit, shared with ``Codec``: an escaped value travels in 16 bits, so |y_hat| > 32767 is clamped in the stream."""
+
+    def __init__(self, model):
+        self.m = model
+        dev = model.device
+        nl = len(model._prior_num_filters) + 1
+        with torch.cuda.device(dev):
+            self.y_tables = DeviceTables(factorized_tables(model._prior_weights, nl), dev)
+
+    def latent_shape(self, H, W):
+        """(C, h, w) of this model's latents for an H x W image (pad to the downsample factor, then the analysis' own shape
+        arithmetic)."""
+        m = self.m
+        f = m.downsample_factor
+        h, w = m._analysis.out_hw(-(-H // f) * f, -(-W // f) * f)
+        return (m._bottleneck_size, h, w)
+
+    def _launch(self, x):
+        """analysis -> the coder's launch(es) (``FUSED_CHANNEL_ENCODE``), on the current stream; no host synchronisation."""
+        m = self.m
+        y = m.infer_latent_rvs(x).uq[0].loc
+        e = y[0].numel()
+        segments = _segments(e)
+        lanes = _lanes(-(-e // segments))
+        if FUSED_CHANNEL_ENCODE:
+            scratch, lens, _ = rans_encode_channels_launch(y, self.y_tables, segments, lanes)
+        else:
+            scratch, lens = rans_encode_launch(round_to_int(y), channel_table_ids(y.shape, y.device), self.y_tables, segments, lanes)
+        return dict(x=x, y=y, segments=segments, lanes=lanes, scratch=scratch, lens=lens)
+
+    def _blob(self, j, lens_h, words):
+        n, H, W, _ = j["x"].shape
+        _, h, w, c = j["y"].shape
+        return pack_v4(ARITH[self.m._precision], n, H, W, c, h, w, j["segments"], j["lanes"], lens_h) + words.tobytes()
+
+    def compress(self, x) -> bytes:
+        m = self.m
+        x = m._as_device_images(x)
+        with torch.cuda.device(m.device):
+            j = self._launch(x)
+            lens_h = j["lens"].cpu().numpy().astype(np.int64)
+            words = rans_encode_finish(j["scratch"], j["lens"], lens_h).cpu().numpy()
+            ops.check_conv_status()       # the copies synchronised the stream: a flagged stream-K launch raises here, not a wrong file
+        return self._blob(j, lens_h, words)
+
+    def compress_many(self, xs):
+        """``compress`` for several batches -> their bitstreams, in order, byte for byte what one ``compress`` per batch returns.
+        The batches' analyses and coder launches run side by side on the library's side streams; the stream lengths of ALL
+        batches come back in one copy, the packed payloads in another (``Codec.compress_many``)."""
+        m = self.m
+        xs = [m._as_device_images(x) for x in xs]
+        if not xs:
+            return []
+        with torch.cuda.device(m.device):
+            main = torch.cuda.current_stream()
+            side = ops.side_streams(len(xs), m.device) if len(xs) > 1 and not torch.cuda.is_current_stream_capturing() else [main] * len(xs)
+            jobs = []
+            for st, x in zip(side, xs):
+                if st is not main:
+                    st.wait_stream(main)
+                with torch.cuda.stream(st):
+                    jobs.append(dict(self._launch(x), st=st))
+            for j in jobs:
+                if j["st"] is not main:
+                    main.wait_stream(j["st"])
+                    for t in (j["scratch"], j["lens"]):
+                        t.record_stream(main)
+            lens_h = torch.cat([j["lens"] for j in jobs]).cpu().numpy().astype(np.int64)                             # read-back 1 of 2
+            pays, o = [], 0
+            for j in jobs:
+                ns = j["lens"].numel()
+                j["lens_h"] = lens_h[o:o + ns]
+                o += ns
+                pays.append(rans_encode_finish(j["scratch"], j["lens"], j["lens_h"]))
+            words = torch.cat(pays).cpu().numpy()                                                                    # read-back 2 of 2
+            ops.check_conv_status()
+        out, o = [], 0
+        for j in jobs:
+            nw = int(j["lens_h"].sum())
+            out.append(self._blob(j, j["lens_h"], words[o:o + nw]))
+            o += nw
+        return out
+
+    def _parse(self, blob: bytes):
+        """Header and stream lengths of one blob, checked against THIS model: nothing later trusts the header."""
+        return parse_v4(blob, ARITH[self.m._precision], self.latent_shape)
+
+    def decompress(self, blob: bytes):
+        return self.decompress_many([blob])[0]
+
+    def decompress_many(self, blobs):
+        """Several bitstreams -> their pixel batches, in order.  ONE upload for every blob's words and stream offsets; the
+        entropy-decoding launches of all blobs run side by side on streams of their own (lone waves whose time is a latency,
+        ``Codec.decompress_many``); the syntheses run on the caller's stream, largest blob first, each as soon as its latents
+        are there.  A synthesis that may run beside another blob's decoding waves takes the static schedules
+        (``ops.static_schedules``: same bits); the last one, and a lone blob's, meet none and keep stream-K.  One read-back
+        of the streams' termination counters, ``ops.check_conv_status()``, then the pixels are returned."""
+        m = self.m
+        if not blobs:
+            return []
+        heads = [self._parse(b) for b in blobs]
+        dev = m.device
+        with torch.cuda.device(dev):
+            main = torch.cuda.current_stream()
+            side = ops.side_streams(len(blobs), dev) if len(blobs) > 1 and not torch.cuda.is_current_stream_capturing() else [main] * len(blobs)
+            bad = torch.zeros((len(blobs),), dtype=torch.int32, device=dev)
+            # ONE upload (int64 offsets first, then the 16-bit words: both aligned)
+            offs = [np.concatenate([[0], np.cumsum(hd["lens"])]).astype(np.int64) for hd in heads]
+            words = [np.frombuffer(b, "<i2", hd["words"], hd["pos"]) for b, hd in zip(blobs, heads)]
+            noff = sum(len(o) for o in offs)
+            host = np.empty(8 * noff + 2 * sum(len(w) for w in words), np.uint8)
+            host[:8 * noff].view(np.int64)[:] = np.concatenate(offs)
+            host[8 * noff:].view(np.int16)[:] = np.concatenate(words)
+            up = torch.from_numpy(host).to(dev)
+            off_d, word_d = up[:8 * noff].view(torch.int64), up[8 * noff:].view(torch.int16)
+            y_hats, o, wpos = [], 0, 0
+            for k, (hd, st) in enumerate(zip(heads, side)):
+                if st is not main:
+                    st.wait_stream(main)
+                with torch.cuda.stream(st):
+                    y_hats.append(rans_decode_channels(word_d[wpos:wpos + hd["words"]], hd["lens"], (hd["n"], hd["h"], hd["w"], hd["c"]),
+                                                       self.y_tables, hd["segments"], hd["lanes"], bad=bad[k:k + 1],
+                                                       offsets=off_d[o:o + len(offs[k])]))
+                if st is not main:
+                    up.record_stream(st)
+                o += len(offs[k])
+                wpos += hd["words"]
+            beside = side[0] is not main
+            order = sorted(range(len(heads)), key=lambda k: -(heads[k]["n"] * heads[k]["h"] * heads[k]["w"]))
+            out = [None] * len(heads)
+            for i, k in enumerate(order):
+                hd, st = heads[k], side[k]
+                if st is not main:
+                    main.wait_stream(st)
+                    y_hats[k].record_stream(main)
+                with ops.static_schedules(beside and i + 1 < len(order)):
+                    out[k] = m.decode(y_hats[k], None, (hd["H"], hd["W"]), check=False)
+            nbad = int(bad.sum().item())                           # synchronises the stream
+            if nbad:
+                total = sum(hd["n"] * hd["segments"] for hd in heads)
+                raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {total} rANS streams did not terminate cleanly")
+            ops.check_conv_status()       # wrong pixels never leave without an error
+            return out

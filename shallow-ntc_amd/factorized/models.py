@@ -1,5 +1,6 @@
 """Factorized-prior model (reference factorized/models.py:39-183): analysis -> round + deep-factorized
-bits -> synthesis.  Same API as mshyper.models.Model; only the three overridden methods differ."""
+bits -> synthesis.  Same API as mshyper.models.Model; only the overridden methods differ.  compress / decompress go through
+entropy_coding.FactorizedCodec (wire format v4: one latent, one table per channel)."""
 from __future__ import annotations
 
 import torch
@@ -86,3 +87,10 @@ class Model(_ms.Model):
             if check:
                 ops.check_conv_status()
         return out
+
+    # -- bitstream: compress / compress_many / decompress / decompress_many are the base class's, on this codec ----------
+    def _get_codec(self):
+        from ..entropy_coding import FactorizedCodec
+        if getattr(self, "_codec", None) is None:
+            self._codec = FactorizedCodec(self)
+        return self._codec
