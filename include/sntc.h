@@ -501,6 +501,37 @@ int sntc_avgpool2_symmetric(const float* x, int n, int h, int w, int c, float* y
 int sntc_pixels_float(const float* x_hat, int n, int h, int w, int c, int hs, int ws, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (MS-)SSIM as a differentiable distortion (csrc/msssim_grad.hip; the quality is reference mshyper/models.py:321-331,
+ *   DESIGN.md 4.6): D = 1 - mean_B q_i on the UNROUNDED, unclamped floats a = (x + .5) 255, b = (x_hat cropped + .5) 255,
+ *   max_val 255.  q_i: single-scale SSIM when both sides are < 160, five-scale MS-SSIM otherwise; every factor max(., 0);
+ *   per channel prod_k f_k^{w_k}, then the mean over channels.  A factor clamped at 0 contributes zero gradient and zeroes the
+ *   gradient of its whole (image, channel) product.  None of these entry points allocates or synchronises.
+ * ------------------------------------------------------------------------------------------ */
+/* a[n,h,w,c], b[n,h,w,c] as above from x[n,h,w,c] and x_hat[n,hs,ws,c]; sse[n] (OVERWRITTEN) as sntc_distortion_grad leaves it
+ * (reference mshyper/models.py:321-331 on the training-mode floats of :313-317). */
+int sntc_msssim_inputs(const float* x, const float* x_hat, int n, int h, int w, int c, int hs, int ws, float* a, float* b,
+                       double* sse, void* stream);
+/* Device-side finish of the 5-factor product (reference mshyper/models.py:321-331): sums[scales, 2, n, c] are the outputs of
+ * sntc_ssim_scale per scale ([k][0] ssim, [k][1] cs), counts[scales] / weights[scales] HOST arrays (filter outputs per scale;
+ * the MS-SSIM power factors, may be NULL when scales == 1 = single-scale SSIM).  -> q[n] (float64) and
+ * coef[scales, n, c] = d(weight * q_i) / d(sum_k): the factor of the cs map's gradient on scales 0 .. last-1 and of the ssim
+ * map's on the last (or single) scale, 0 for a product with a clamped factor.  weight = -lambda / n for rd_loss. */
+int sntc_msssim_finish(const double* sums, const double* counts, const double* weights, int scales, int n, int c, double weight,
+                       double* q, float* coef, void* stream);
+/* One scale of the gradient (reference mshyper/models.py:321-331), c in {1, 3}, one launch: for every pixel r of b
+ *   g(r) = coef[n, c] ((w * A)(r) + a(r) (w * B)(r) + 2 b(r) (w * C)(r)) + 1/4 g_coarse(floor(r / 2)) [x 2 per replicated edge]
+ * with A, B, C the partial derivatives of the cs map (use_lum = 0) or the ssim = luminance * cs map (use_lum = 1) w.r.t.
+ * mu_b, E[ab], E[a^2 + b^2] at each filter output, and w * the full (adjoint-of-VALID) 11-tap separable correlation.
+ * g_coarse[n, ceil(h/2), ceil(w/2), c] is the next scale's gradient or NULL.  g[n, hs, ws, c] (hs >= h, ws >= w) is
+ * OVERWRITTEN with out_scale * g(r), zeros in the margin (scale 0: the padded x_hat shape and out_scale = 255). */
+int sntc_ssim_scale_grad(const float* a, const float* b, int n, int h, int w, int c, float max_val, const float* coef, int use_lum,
+                         const float* g_coarse, int hs, int ws, float out_scale, float* g, void* stream);
+/* Adjoint of sntc_avgpool2_symmetric (reference mshyper/models.py:321-331, the pooling between MS-SSIM scales):
+ * g_fine[n, h, w, c] (OVERWRITTEN) from g_coarse[n, ceil(h/2), ceil(w/2), c]; the replicated last row / column of an odd size
+ * receives both of its contributions. */
+int sntc_avgpool2_symmetric_grad(const float* g_coarse, int n, int h, int w, int c, float* g_fine, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * SGA iterative inference (config 5): element-wise pieces of Model.itinf_train_step,
  *   mshyper/models.py:397-408 with frame_loss_given_latent_rvs(training=True), :260-268,285-291,343.
  *   The contractions of the backward pass are sntc_conv_forward calls: the input gradient of

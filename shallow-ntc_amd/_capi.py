@@ -141,6 +141,12 @@ SIGNATURES = {
     "sntc_ssim_scale": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
     "sntc_avgpool2_symmetric": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "sntc_pixels_float": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "sntc_msssim_inputs": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "sntc_msssim_finish": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_double,
+                                     _P, _P, _P]),
+    "sntc_ssim_scale_grad": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int, _P, C.c_int, C.c_int,
+                                       C.c_float, _P, _P]),
+    "sntc_avgpool2_symmetric_grad": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "sntc_sga_factorized_fwd": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_float, _P, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P]),
     "sntc_sga_normal_fwd": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_float, _P, C.c_uint64, C.c_uint64, _P, _P, _P,
                                       _P, _P, _P]),

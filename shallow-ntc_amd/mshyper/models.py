@@ -93,8 +93,13 @@ class Model:
     def __init__(self, scheduled_num_steps=1500000, rd_lambda=0.01, offset_heuristic=True,
                  transform_config=EMPTY_DICT, optimizer_config=EMPTY_DICT,
                  latent_config=None, profile=False, device=None, prior_num_filters=(3, 3), seed=4321,
-                 quality_metrics=True, precision="fp32"):
-        """``precision``: "fp32" (default: exact fp32 MFMA everywhere, the reference's arithmetic) or "bf16x3": the
+                 quality_metrics=True, precision="fp32", distortion="mse"):
+        """``distortion``: "mse" (default) or "ms_ssim": what SGA iterative inference (``itinf_train_step``) descends.
+        "ms_ssim": rd_loss = bpp + rd_lambda * (1 - mean_B q_i), q_i the (MS-)SSIM of reference :321-331 on the unrounded
+        0-255 floats (single-scale SSIM when both sides are < 160).  rd_lambda is NOT rescaled: 1 - q lies in
+        [0, 1] where the MSE of 0-255 pixels runs to the hundreds, so useful values are orders of magnitude larger than for
+        "mse".  Images on which the metric is not computable raise ValueError; training (``train_step``) is MSE only.
+        ``precision``: "fp32" (default: exact fp32 MFMA everywhere, the reference's arithmetic) or "bf16x3": the
         convolutions that qualify (Cin % 16 == 0, at least one 256-row strip per image) run the split-precision contraction
         on pre-split operands (csrc/bf3_gemm.hip; ~fp32 accuracy, not bit-identical to it).  An encoder and a decoder must
         use the same precision: the bitstream header carries it."""
@@ -114,6 +119,9 @@ class Model:
         if precision not in ("fp32", "bf16x3"):
             raise ValueError(f"precision must be 'fp32' or 'bf16x3', not {precision!r}")
         self._precision = precision
+        if distortion not in ("mse", "ms_ssim"):
+            raise ValueError(f"distortion must be 'mse' or 'ms_ssim', not {distortion!r}")
+        self._distortion = distortion
         self._seed = seed
         self._quality_metrics = quality_metrics     # MS-SSIM at eval (reference :321-331); LPIPS is not vendored
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -321,9 +329,14 @@ class Model:
             recon = self._synthesis(y_dec, training=True)                                         # :297
             sse = ops.float_sse(x, recon)                                                         # unpad + 0-255 floats, unrounded
             rows = [bits_y if bits_z is None else bits_z, bits_y, sse]
+            msssim = None
+            if self._distortion == "ms_ssim":                                                     # the same unrounded floats
+                ops.msssim_scale_sizes(x.shape[1], x.shape[2])
+                a, b, _ = ops.msssim_inputs(x, recon)
+                msssim = ops.image_quality(a, b, 255.0)
             host = torch.stack(rows).cpu().numpy()
             ops.check_conv_status()
-        rd_loss, metrics = self._finish_metrics(x.shape, None if bits_z is None else host[0], host[1], host[2])
+        rd_loss, metrics = self._finish_metrics(x.shape, None if bits_z is None else host[0], host[1], host[2], msssim)
         metrics.record_image("reconstruction", recon)
         return rd_loss, metrics
 
@@ -357,6 +370,9 @@ class Model:
 
     def _msssim_applies(self, h, w):
         """reference :321-331: (MS-)SSIM of the uint8-quantised images whenever TensorFlow itself can compute it."""
+        if self._distortion == "ms_ssim":      # the loss itself: computed wherever the kernels can, ValueError elsewhere
+            ops.msssim_scale_sizes(h, w)
+            return True
         if not self._quality_metrics or min(h, w) < 11:
             return False
         # the reference switches to ssim_multiscale once either side reaches 160 (:325-329), which TensorFlow itself
@@ -387,6 +403,10 @@ class Model:
         mse, psnr = np.float32(mses.mean(dtype=np.float32)), np.float32(psnrs.mean(dtype=np.float32))
         lam = self._scheduled_rd_lambda if sched is None else sched[1]
         rd_loss = np.float32(bpp + np.float32(lam) * mse)                               # :343
+        if self._distortion == "ms_ssim":                                               # bpp + lambda (1 - mean_B q_i)
+            if msssim is None:
+                raise ValueError("distortion='ms_ssim': no (MS-)SSIM was computed for this frame")
+            rd_loss = np.float32(bpp + np.float32(lam) * np.float32(1.0 - np.asarray(msssim, np.float64).mean()))
         if not np.isfinite(rd_loss):                                                    # :356
             raise capi.NonFiniteError(capi.ERR_NONFINITE, "rd_loss : Tensor had NaN/Inf values")
         metrics = Metrics.make()
@@ -627,6 +647,8 @@ class Model:
         reference :375-383); returns Metrics with the reference's scalar keys.  The training state (flat parameter /
         gradient / moment buffers, adjoint plans) lives in ``shallow_ntc_amd.train.Trainer`` and is created on first
         use; ``self.trainer.sync_model()`` loads the trained variables back into the inference path."""
+        if self._distortion != "mse":
+            raise NotImplementedError("train_step optimises bpp + lambda * MSE only: distortion='ms_ssim' drives SGA iterative inference")
         if getattr(self, "trainer", None) is None:
             from ..train import Trainer
             self.trainer = Trainer(self, seed=self._seed)
@@ -641,6 +663,8 @@ class Model:
         from ..sga import SGAEngine
         if self._optimizer_config.get("global_clipnorm") is not None:
             raise NotImplementedError("gradient clipping is not used by the reference's itinf config")
+        if self._distortion == "ms_ssim":                               # ValueError where the loss is not computable
+            ops.msssim_scale_sizes(*tuple(image_batch.shape)[1:3])
         self.latent_rvs = self.infer_latent_rvs(image_batch).get_trainable_copy()
         self._sga = getattr(self, "_sga", None) or SGAEngine(self)
         self._adam = [dict(m=torch.zeros_like(rv.loc), v=torch.zeros_like(rv.loc)) for rv in self.latent_rvs.uq]
@@ -654,7 +678,8 @@ class Model:
 
     def itinf_train_step(self, image_batch, noise=None, seed=0, fetch=True):
         """One SGA step: loss = bpp + lambda * MSE(unrounded 0-255 floats), gradients to [z_loc, y_loc] only,
-        Keras-Adam update (:397-408).  ``noise`` = (gumbel_z, gumbel_y) makes the step deterministic.
+        Keras-Adam update (:397-408).  With ``distortion="ms_ssim"`` the loss is bpp + lambda * (1 - mean_B (MS-)SSIM) of the
+        same floats; the metrics then add ``msssim`` / ``msssim_db`` and ``rd_loss`` follows that definition.  ``noise`` = (gumbel_z, gumbel_y) makes the step deterministic.
         ``fetch`` False: the step's three scalars stay on the device and nothing synchronises (the reference's step is a
         tf.function whose metrics are only converted where the loop logs them, common/itinf_lib.py:67-75); returns None, and
         ``itinf_last_metrics()`` fetches the most recent step's metrics when the caller wants them."""
@@ -662,6 +687,8 @@ class Model:
         cfg = self.latent_config["uq"]
         if cfg.get("method") != "sga":
             raise NotImplementedError("itinf_train_step implements latent_config uq.method == 'sga'")
+        if self._distortion == "ms_ssim":                               # never a silent fall-back to MSE: refuse before any launch
+            ops.msssim_scale_sizes(x.shape[1], x.shape[2])
         tau = cfg["tau"]
         lr = self._scheduled_lr
         locs = [rv.loc for rv in self.latent_rvs.uq]                     # (z_loc, y_loc); the factorized model: (y_loc,)
@@ -676,7 +703,8 @@ class Model:
                 ops.adam_step(p, g, st["m"], st["v"], lr, t, self._optimizer_config.get("beta_1", 0.9),
                               self._optimizer_config.get("beta_2", 0.999), self._optimizer_config.get("epsilon", 1e-7))
             # the metrics depend on (step, lr, lambda, tau) of THIS step: keep them with the device scalars
-            self._itinf_pending = dict(dev=torch.stack([r["bits_z"], r["bits_y"], r["sse"]]), shape=tuple(x.shape), two=len(locs) == 2,
+            rows = [r["bits_z"], r["bits_y"], r["sse"]] + ([r["msssim"]] if "msssim" in r else [])
+            self._itinf_pending = dict(dev=torch.stack(rows), shape=tuple(x.shape), two=len(locs) == 2,
                                        scalars=(self._scheduled_lr, self._scheduled_rd_lambda, tau))
         self._itinf_step += 1
         self.last_grads = tuple(grads)
@@ -691,7 +719,8 @@ class Model:
         with torch.cuda.device(self.device):
             host = pend["dev"].cpu().numpy()
             ops.check_conv_status()
-        _, metrics = self._finish_metrics(pend["shape"], host[0] if pend["two"] else None, host[1], host[2], sched=pend["scalars"])
+        _, metrics = self._finish_metrics(pend["shape"], host[0] if pend["two"] else None, host[1], host[2],
+                                          msssim=host[3] if len(host) > 3 else None, sched=pend["scalars"])
         return metrics
 
     def itinf_validation_step(self, image_batch, training=False) -> Metrics:

@@ -1460,3 +1460,102 @@ def image_quality(a, b, max_val=255.0):
     The kernels leave per-(image, channel) sums; the 5-factor geometric mean is finished on the host."""
     sums, counts, single = image_quality_launch(a, b, max_val)
     return image_quality_finish(sums.cpu().numpy(), counts, single)
+
+
+# ------------------------------------------------------------------------------------------
+# (MS-)SSIM as a differentiable distortion (csrc/msssim_grad.hip, DESIGN.md 4.6)
+# ------------------------------------------------------------------------------------------
+def msssim_scale_sizes(h, w):
+    """Sizes of the scales ``image_quality`` evaluates on an h x w image (reference mshyper/models.py:321-331): one when both
+    sides are < 160, five otherwise.  Raises ValueError where the metric is not computable: a side shorter than the 11-tap
+    window, or MS-SSIM selected and its fifth scale smaller than the window."""
+    if min(h, w) < 11:
+        raise ValueError(f"(MS-)SSIM needs both sides >= 11 (the 11 x 11 window), not {h} x {w}")
+    if h < 160 and w < 160:
+        return [(h, w)]
+    sizes = [(h, w)]
+    for _ in range(len(MSSSIM_WEIGHTS) - 1):
+        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    if min(sizes[-1]) < 11:
+        raise ValueError(f"MS-SSIM of a {h} x {w} image: the fifth scale ({sizes[-1][0]} x {sizes[-1][1]}) is smaller than "
+                         "the 11 x 11 window")
+    return sizes
+
+
+def msssim_inputs(x, x_hat):
+    """reference mshyper/models.py:321-331 on the training-mode floats: -> (a, b, sse[n]) with a = (x + .5) 255 and
+    b = (x_hat cropped to x + .5) 255, unrounded and unclamped, and the per-image SSE of ``distortion_grad``."""
+    _check_nhwc(x)
+    _check_nhwc(x_hat, x.shape[-1])
+    n, h, w, c = x.shape
+    a, b = torch.empty_like(x), torch.empty_like(x)
+    sse = torch.empty((n,), dtype=torch.float64, device=x.device)
+    capi.call("sntc_msssim_inputs", _ptr(x), _ptr(x_hat), n, h, w, c, x_hat.shape[1], x_hat.shape[2], _ptr(a), _ptr(b), _ptr(sse),
+              _stream())
+    return a, b, sse
+
+
+def msssim_finish(sums, counts, single, weight):
+    """Device-side ``image_quality_finish`` (reference mshyper/models.py:321-331): -> (q[n] float64, coef[scales, n, c] float32 =
+    d(weight q_i) / d(sum_k) of the cs map (ssim map on the last or single scale); zero where a factor is clamped)."""
+    scales, _, n, c = sums.shape
+    q = torch.empty((n,), dtype=torch.float64, device=sums.device)
+    coef = torch.empty((scales, n, c), dtype=torch.float32, device=sums.device)
+    cnt = (C.c_double * scales)(*counts)
+    wts = None if single else (C.c_double * scales)(*MSSSIM_WEIGHTS[:scales])
+    capi.call("sntc_msssim_finish", _ptr(sums), cnt, wts, scales, n, c, float(weight), _ptr(q), _ptr(coef), _stream())
+    return q, coef
+
+
+def ssim_scale_grad(a, b, coef, use_lum, g_coarse=None, out=None, out_scale=1.0, max_val=255.0):
+    """One scale of the (MS-)SSIM gradient w.r.t. ``b`` with the pool adjoint of ``g_coarse`` fused in (reference
+    mshyper/models.py:321-331).  ``out`` [n, hs >= h, ws >= w, c] receives ``out_scale`` times it, zeros in the margin."""
+    _check_nhwc(a)
+    _check_nhwc(b, a.shape[-1])
+    n, h, w, c = a.shape
+    if out is None:
+        out = torch.empty_like(b)
+    capi.call("sntc_ssim_scale_grad", _ptr(a), _ptr(b), n, h, w, c, float(max_val), _ptr(coef), int(use_lum), _ptr(g_coarse),
+              out.shape[1], out.shape[2], float(out_scale), _ptr(out), _stream())
+    return out
+
+
+def avgpool2_symmetric_grad(g_coarse, h, w):
+    """Adjoint of the 2 x 2 symmetric-extended average pool between MS-SSIM scales (reference mshyper/models.py:321-331):
+    g_coarse [n, ceil(h/2), ceil(w/2), c] -> [n, h, w, c]."""
+    _check_nhwc(g_coarse)
+    n, hc, wc, c = g_coarse.shape
+    if (hc, wc) != ((h + 1) // 2, (w + 1) // 2):
+        raise ValueError(f"g_coarse is {hc} x {wc}, the pool of {h} x {w} is {(h + 1) // 2} x {(w + 1) // 2}")
+    out = torch.empty((n, h, w, c), dtype=torch.float32, device=g_coarse.device)
+    capi.call("sntc_avgpool2_symmetric_grad", _ptr(g_coarse), n, h, w, c, _ptr(out), _stream())
+    return out
+
+
+def msssim_distortion_grad(x, x_hat, lam):
+    """Value and gradient of the (MS-)SSIM distortion of the SGA step, rd_loss = bpp + lam (1 - mean_B q_i) (reference
+    mshyper/models.py:321-331 for q_i, on the unrounded 0-255 floats of ``msssim_inputs``): -> (g_xhat with x_hat's (padded)
+    shape = d(lam (1 - mean q)) / d x_hat, sse[n] as ``distortion_grad`` leaves it, q[n] float64).  All three stay on the
+    device and nothing synchronises: the forward launches of ``image_quality_launch``, the device-side finish, then one
+    gradient launch per scale, coarse to fine.  Raises ValueError where the metric is not computable."""
+    _check_nhwc(x)
+    _check_nhwc(x_hat, x.shape[-1])
+    n, h, w, c = x.shape
+    if c not in (1, 3):
+        raise ValueError(f"(MS-)SSIM kernels exist for 1 or 3 channels, not {c}")
+    sizes = msssim_scale_sizes(h, w)
+    scales, single = len(sizes), len(sizes) == 1
+    a, b, sse = msssim_inputs(x, x_hat)
+    pyramid = [(a, b)]
+    sums = torch.empty((scales, 2, n, c), dtype=torch.float64, device=x.device)
+    counts = []
+    for k in range(scales):
+        if k > 0:
+            pyramid.append((_avgpool2(pyramid[-1][0]), _avgpool2(pyramid[-1][1])))
+        counts.append(_ssim_scale(pyramid[k][0], pyramid[k][1], 255.0, sums[k]))
+    q, coef = msssim_finish(sums, counts, single, -float(lam) / n)
+    g = None
+    for k in range(scales - 1, -1, -1):
+        out = torch.empty_like(x_hat) if k == 0 else None
+        g = ssim_scale_grad(pyramid[k][0], pyramid[k][1], coef[k], k == scales - 1, g, out, 255.0 if k == 0 else 1.0)
+    return g, sse, q

@@ -127,10 +127,13 @@ def make_backward(transform):
 class SGAEngine:
     """loss(z_loc, y_loc) = bpp + lambda * MSE_255 of frame_loss_given_latent_rvs(training=True) with the
     'sga' uq method, and its gradients w.r.t. (z_loc, y_loc) only (mshyper/models.py:397-399).  The factorized-prior model
-    (factorized/models.py:108-118) has one latent: y~ = sga_round(y_loc), coded by the deep-factorized prior."""
+    (factorized/models.py:108-118) has one latent: y~ = sga_round(y_loc), coded by the deep-factorized prior.
+    A model built with ``distortion="ms_ssim"`` descends bpp + lambda * (1 - mean_B (MS-)SSIM) instead; the
+    result then also carries ``msssim`` (per-image q, float64, on the device)."""
 
     def __init__(self, model):
         self.m = model
+        self.distortion = getattr(model, "_distortion", "mse")
         with torch.cuda.device(model.device):
             self.hyper = None if model.factorized else GradChain(model._hyper_synthesis)
             self.syn = make_backward(model._synthesis)
@@ -140,20 +143,28 @@ class SGAEngine:
         n, h, w, c = x.shape
         w_bpp = 1.0 / (n * h * w)                                      # bpp = mean_B(bits) / (H W)   (:302-307)
         scale = rd_lambda * 2.0 * 255.0 * 255.0 / (n * h * w * c)     # d(lambda * mean_B mean_HWC (255 d)^2)/d x_hat
+        extra = {}
+
+        def distortion_grad(recon):
+            if self.distortion == "mse":
+                return ops.distortion_grad(x, recon, scale)
+            g_x, sse, extra["msssim"] = ops.msssim_distortion_grad(x, recon, rd_lambda)
+            return g_x, sse
+
         if m.factorized:
             y_t, sp_y, dby, bits_y = ops.sga_factorized_fwd(m._get_prior(), y_loc, tau, noise_y, seed, step)   # factorized :108-116
             recon, cache = self.syn.forward(y_t)
-            g_x, sse = ops.distortion_grad(x, recon, scale)
+            g_x, sse = distortion_grad(recon)
             g_y = ops.sga_chain(self.syn.backward(g_x, cache), dby, sp_y, w_bpp)
             return dict(bits_z=torch.zeros_like(bits_y), bits_y=bits_y, sse=sse, g_z=None, g_y=g_y, recon=recon, z_tilde=None,
-                        y_tilde=y_t)
+                        y_tilde=y_t, **extra)
         z_t, sp_z, dbz, bits_z = ops.sga_factorized_fwd(m._get_prior(), z_loc, tau, noise_z, seed, step)     # :262-268
         hyper, acts = self.hyper.forward(z_t)                                                              # :273
         y_t, sp_y, dv, dr, bits_y = ops.sga_normal_fwd(y_loc, hyper, tau, noise_y, seed, step)             # :285-291
         recon, cache = self.syn.forward(y_t)
-        g_x, sse = ops.distortion_grad(x, recon, scale)                                                    # :313-317,343
+        g_x, sse = distortion_grad(recon)                                                                  # :313-317,343
         g_yt = self.syn.backward(g_x, cache)
         g_y, g_hyper = ops.sga_normal_bwd(g_yt, sp_y, dv, dr, w_bpp)
         g_zt = self.hyper.backward(g_hyper, acts)
         g_z = ops.sga_chain(g_zt, dbz, sp_z, w_bpp)
-        return dict(bits_z=bits_z, bits_y=bits_y, sse=sse, g_z=g_z, g_y=g_y, recon=recon, z_tilde=z_t, y_tilde=y_t)
+        return dict(bits_z=bits_z, bits_y=bits_y, sse=sse, g_z=g_z, g_y=g_y, recon=recon, z_tilde=z_t, y_tilde=y_t, **extra)

@@ -408,6 +408,8 @@ class Trainer:
     BUCKETS = ("synthesis", "prior", "hyper_synthesis", "hyper_analysis", "analysis")   # backward order
 
     def __init__(self, model, seed=0):
+        if getattr(model, "_distortion", "mse") != "mse":
+            raise NotImplementedError("training optimises bpp + lambda * MSE only: the MS-SSIM distortion is wired into SGA iterative inference")
         self.factorized = bool(model.factorized)
         if self.factorized:                 # factorized/models.py: no hyper transforms, the prior codes y itself
             self.BUCKETS = ("synthesis", "prior", "analysis")
