@@ -479,6 +479,16 @@ int sntc_rans_decode_channels(const uint16_t* payload, const int64_t* offsets, i
                               int segments, int lanes, const uint16_t* cdf, const uint32_t* meta, int total_entries,
                               const uint32_t* dec, const uint16_t* lut, const uint32_t* lut_meta, int lut_entries, float* y_hat,
                               int32_t* bad_streams, void* stream);
+/* What the streams of sntc_rans_encode pay for the symbols of `values`, without coding them (the reference has no bitstream,
+ *   compression=False at mshyper/models.py:246-251, and scores latents by the continuous estimate only):
+ *   cost[b] = sum over image b's elements of cost_q[offset_t + symbol], t = the element's table id and symbol = value - vmin_t,
+ *   or ESCAPE (the table's last symbol) when that is < 0 or >= n_t - 1 -- the encoder's own rule.
+ *   cost_q: uint32, one entry per cdf entry at the same offsets, = rint((16 - log2(freq)) * 65536), ESCAPE entries + 16 * 65536
+ *   (the raw 16-bit value): the unit is 2^-16 bit.  cost: uint64 [nimages], zeroed by the call.  All sums are integers:
+ *   the result is the exact sum whatever the launch geometry.  Table ids must be < ntables (not checked, as in the coder).
+ *   Not included: the flushed lane states (32 bits per lane and stream) and the states' renormalisation slack. */
+int sntc_rans_cost(const int32_t* values, const uint16_t* table_ids, int nimages, int64_t elems_per_image, const uint32_t* meta,
+                   int ntables, int total_entries, const uint32_t* cost_q, uint64_t* cost, void* stream);
 /* table id of every y element = round(clamp(exp(raw), 0, 63)), raw = hyper[..., c:]; of every z element = channel */
 int sntc_scale_table_ids(const float* hyper, int64_t npix, int c, uint16_t* table_ids, void* stream);
 /* table id = channel (deep-factorized prior: one table per channel). */

@@ -134,6 +134,7 @@ SIGNATURES = {
     "sntc_rans_decode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P]),
     "sntc_rans_encode_channels": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int64, _P, _P, _P, _P]),
     "sntc_rans_decode_channels": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P]),
+    "sntc_rans_cost": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, C.c_int, C.c_int, _P, _P, _P]),
     "sntc_scale_table_ids": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
     "sntc_channel_table_ids": (C.c_int, [C.c_int64, C.c_int, _P, _P]),
     "sntc_round_to_int": (C.c_int, [_P, C.c_int64, _P, _P]),

@@ -81,10 +81,10 @@ __global__ void __launch_bounds__(64) rans_encode_channels_kernel(const float* _
   struct Sym { unsigned f, c, raw; bool active, esc; };
   auto lookup = [&](int t, int v, uint2 m) -> Sym {
     const bool active = t != kNoTable;
-    const int n = (int)(m.y >> 16), vmin = (int)(short)(m.y & 0xffffu);
-    int sym = v - vmin;
-    const bool esc = active && (sym < 0 || sym >= n - 1);
-    if (esc) sym = n - 1;
+    const int n = (int)(m.y >> 16);
+    bool esc;
+    int sym = rans_symbol(v, m, esc);
+    esc = active && esc;
     if (!active) sym = 0;
     const unsigned cl = cdf[m.x + sym];
     const unsigned ch = sym + 1 < n ? (unsigned)cdf[m.x + sym + 1] : 65536u;

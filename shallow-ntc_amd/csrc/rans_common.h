@@ -1,5 +1,6 @@
-// rans_common.h -- what the two rANS translation units share: the table views, the staging constants and the host-side
-// stream arithmetic.  rans.hip codes with a table id per element; rans_channels.hip with table = channel, from / to floats.
+// rans_common.h -- what the rANS translation units share: the table views, the symbol of a value, the staging constants and
+// the host-side stream arithmetic.  rans.hip codes with a table id per element; rans_channels.hip with table = channel, from /
+// to floats; rans_cost.hip sums what the coded symbols cost.
 // The stream format is described once, at the head of rans.hip.
 #pragma once
 #include "sntc_internal.h"
@@ -55,6 +56,16 @@ __device__ __forceinline__ void rans_stage_tables(const RansTables& T, unsigned 
     meta = T.meta;
     cdf = T.cdf;
   }
+}
+
+// The symbol a value takes in the table of descriptor m (RansTables::meta): v - vmin where that is one of the table's n - 1
+// real symbols, else ESCAPE (the last symbol, n - 1; the value itself then travels as a raw 16-bit word).  The encoders code
+// this symbol and sntc_rans_cost prices it: one definition, so the price is that of the word stream.
+__device__ __forceinline__ int rans_symbol(int v, uint2 m, bool& esc) {
+  const int n = (int)(m.y >> 16), vmin = (int)(short)(m.y & 0xffffu);
+  const int sym = v - vmin;
+  esc = sym < 0 || sym >= n - 1;
+  return esc ? n - 1 : sym;
 }
 
 // elements of one segment: an image's elements cut into `segments` runs, each a multiple of 64

@@ -142,6 +142,23 @@ def start_tables(cdfs, bits):
     return flat, np.asarray(lmeta, np.uint32)
 
 
+COST_UNIT = 1 << 16                      # ``rans_cost`` counts in 2^-16 bit
+RANS_COST_THREADS, RANS_COST_VEC = 1024, 4      # csrc/rans_cost.hip: a workgroup takes 1024 elements per pass, 4096 where the
+                                                # image's element count is a multiple of 4 (tests place sizes around both)
+
+
+def cost_table(tabs):
+    """What a symbol of each table costs the rANS coder, in units of 2^-16 bit: entry s of table t = rint((16 - log2 f_s) * 65536)
+    with f_s the integer frequency the coder uses; the last entry of every table (ESCAPE) carries the 16 raw bits of the
+    escaped value on top.  -> uint32, one entry per cdf entry, tables back to back (the offsets of ``DeviceTables.cdf``)."""
+    out = []
+    for _, f in tabs:
+        c = np.rint((PRECISION - np.log2(np.asarray(f, np.float64))) * COST_UNIT).astype(np.int64)
+        c[-1] += 16 * COST_UNIT
+        out.append(c)
+    return np.concatenate(out).astype(np.uint32)
+
+
 class DeviceTables:
     """Concatenated uint16 CDFs (cdf[n] = 65536 implicit) + packed per-table descriptors on the device."""
 
@@ -162,6 +179,7 @@ class DeviceTables:
         self.ntables, self.total = len(tabs), pos
         self.cdf = torch.from_numpy(flat.view(np.int16).copy()).to(device)
         self.meta = torch.from_numpy(np.asarray(meta, np.uint32).view(np.int32).copy()).to(device)
+        self.cost_q = torch.from_numpy(cost_table(tabs).view(np.int32).copy()).to(device)      # sntc_rans_cost: same offsets as cdf
         # the decoder's own view of the tables (include/sntc.h, sntc_rans_decode): packed (start, frequency - 1) entries with
         # three sentinels per table, and start tables of about one entry per symbol -- a table of n symbols gets 2^ceil(log2 n)
         # buckets, one bit more where the CU's LDS has the room, fewer where it has not
@@ -271,6 +289,21 @@ def rans_decode(payload, lens_h, table_ids, shape, tables: DeviceTables, segment
         if nbad:
             raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {n * segments} rANS streams did not terminate cleanly")
     return values
+
+
+def rans_cost(values, table_ids, tables: DeviceTables):
+    """What ``rans_encode`` would pay for the symbols of ``values`` (int32 [n, ...], ``table_ids`` as there), without coding
+    them: -> int64 [n] on the device, in units of 2^-16 bit (divide by ``COST_UNIT`` for bits), the exact integer sum of
+    ``tables.cost_q`` over each image's symbols.  No host synchronisation.  The flushed lane states and the coder's
+    renormalisation slack come on top in the file."""
+    if values.dtype != torch.int32 or table_ids.dtype != torch.int16 or not values.is_contiguous() or not table_ids.is_contiguous() \
+            or values.numel() != table_ids.numel():
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "rans_cost: values int32 and table_ids int16 (uint16 storage), contiguous, of one size")
+    n = values.shape[0]
+    cost = torch.empty((n,), dtype=torch.int64, device=values.device)
+    capi.call("sntc_rans_cost", _p(values), _p(table_ids), n, values.numel() // n, _p(tables.meta), tables.ntables, tables.total,
+              _p(tables.cost_q), _p(cost), ops._stream())
+    return cost
 
 
 def rans_encode_channels_launch(y, tables: DeviceTables, segments=None, lanes=None, want_y_hat=False):
@@ -384,32 +417,87 @@ class Codec:
         hz, wz = m._hyper_analysis.out_hw(h, w)
         return (m._bottleneck_size, m._hyper_bottleneck_size, hz, wz, h, w)
 
+    def _check_latents(self, z, y, image_hw):
+        H, W = int(image_hw[0]), int(image_hw[1])
+        c, cz, hz, wz, h, w = self.latent_shapes(H, W)
+        n = z.shape[0]
+        if tuple(z.shape) != (n, hz, wz, cz) or tuple(y.shape) != (n, h, w, c):
+            raise capi.SntcError(capi.ERR_BAD_SHAPE, f"latents {tuple(z.shape)} / {tuple(y.shape)} are not this model's for {n} images of "
+                                 f"{H} x {W}: {(n, hz, wz, cz)} / {(n, h, w, c)}")
+        return n, H, W
+
+    def _symbols(self, z, y):
+        """(z_loc, y_loc) -> what the file carries: (zi int32, z's table ids, y symbols int32, y's table ids, hyper)."""
+        m = self.m
+        zi = round_to_int(z)
+        hyper = m._hyper_synthesis(int_to_float(zi))
+        _, _, sym = ops.entropy_scale_normal(y, hyper, want_symbols=True)
+        return zi, channel_table_ids(z.shape, m.device), sym, scale_table_ids(hyper), hyper
+
+    def _launch_latents(self, z, y, image_hw):
+        """The device half of ``compress_latents`` on the current stream, no host synchronisation."""
+        n, H, W = self._check_latents(z, y, image_hw)
+        zi, ztid, sym, ytid, _ = self._symbols(z, y)
+        sz, sy = _segments(zi[0].numel()), _segments(sym[0].numel())
+        lz, ly = _lanes(-(-zi[0].numel() // sz)), _lanes(-(-sym[0].numel() // sy))
+        zs, zlen = rans_encode_launch(zi, ztid, self.z_tables, sz, lz)
+        ys, ylen = rans_encode_launch(sym, ytid, self.y_tables, sy, ly)
+        return dict(n=n, H=H, W=W, z=z, y=y, sz=sz, sy=sy, lz=lz, ly=ly, zs=zs, zlen=zlen, ys=ys, ylen=ylen)
+
+    def _finish(self, jobs):
+        """Launched jobs -> their blobs: the stream lengths of ALL jobs come back in one copy, the packed payloads in another."""
+        m = self.m
+        lens_h = torch.cat([t for j in jobs for t in (j["zlen"], j["ylen"])]).cpu().numpy().astype(np.int64)     # read-back 1 of 2
+        pays, o = [], 0
+        for j in jobs:
+            nz, ny = j["zlen"].numel(), j["ylen"].numel()
+            j["zl"], j["yl"] = lens_h[o:o + nz], lens_h[o + nz:o + nz + ny]
+            o += nz + ny
+            pays += [rans_encode_finish(j["zs"], j["zlen"], j["zl"]), rans_encode_finish(j["ys"], j["ylen"], j["yl"])]
+        words = torch.cat(pays).cpu().numpy()                                                                    # read-back 2 of 2
+        ops.check_conv_status()       # the copies synchronised the stream: a flagged stream-K launch raises here, not a wrong file
+        out, o = [], 0
+        for j in jobs:
+            z, y = j["z"], j["y"]
+            zw, yw = int(j["zl"].sum()), int(j["yl"].sum())
+            head = MAGIC + struct.pack(self.HEAD, VERSION | (ARITH[m._precision] << 8), j["n"], j["H"], j["W"], y.shape[-1], z.shape[-1],
+                                       z.shape[1], z.shape[2], y.shape[1], y.shape[2], j["sz"], j["sy"], j["lz"], j["ly"])
+            out.append(head + j["zl"].astype("<u4").tobytes() + j["yl"].astype("<u4").tobytes() + words[o:o + zw + yw].tobytes())
+            o += zw + yw
+        return out
+
+    def compress_latents(self, z_loc, y_loc, image_hw) -> bytes:
+        """Latents of this model for images of ``image_hw`` = (H, W) -- the encoder's, or ones refined by iterative inference --
+        -> the bitstream ``decompress`` reads: z is rounded, the hyper-synthesis gives mu / the scale indexes, y - mu is rounded,
+        both are coded.  ``compress(x)`` is this on ``infer_latent_rvs(x)``."""
+        m = self.m
+        with torch.cuda.device(m.device):
+            return self._finish([self._launch_latents(z_loc.contiguous(), y_loc.contiguous(), image_hw)])[0]
+
+    def latents_cost(self, z_loc, y_loc, x):
+        """What ``compress_latents`` would write for these latents and what ``decompress`` would make of it, without writing it:
+        -> (cost_z, cost_y int64 [n] in 2^-16 bit (``rans_cost``), uint8 pixels, integer SSE [n] against ``x``), all on the
+        device, no host synchronisation."""
+        m = self.m
+        n, H, W = self._check_latents(z_loc, y_loc, x.shape[1:3])
+        zi, ztid, sym, ytid, hyper = self._symbols(z_loc.contiguous(), y_loc.contiguous())
+        cost_z, cost_y = rans_cost(zi, ztid, self.z_tables), rans_cost(sym, ytid, self.y_tables)
+        y_hat = ops.dequant_split3(sym, hyper) if m._synthesis.takes_s3(sym.shape[1], sym.shape[2]) else ops.dequant_scale_normal(sym, hyper)
+        px, sse = m._pixels(y_hat, (H, W), x)                     # the decoder's own steps from the symbols on
+        return cost_z, cost_y, px, sse
+
     def compress(self, x) -> bytes:
         m = self.m
         x = m._as_device_images(x)
-        n, H, W, _ = x.shape
         with torch.cuda.device(m.device):
             lat = m.infer_latent_rvs(x)
-            z, y = lat.uq[0].loc, lat.uq[1].loc
-            zi = round_to_int(z)
-            z_hat = int_to_float(zi)
-            hyper = m._hyper_synthesis(z_hat)
-            _, _, sym = ops.entropy_scale_normal(y, hyper, want_symbols=True)
-            sz, sy = _segments(zi[0].numel()), _segments(sym[0].numel())
-            lz, ly = _lanes(-(-zi[0].numel() // sz)), _lanes(-(-sym[0].numel() // sy))
-            zp, zl = rans_encode(zi, channel_table_ids(z.shape, m.device), self.z_tables, sz, lz)
-            yp, yl = rans_encode(sym, scale_table_ids(hyper), self.y_tables, sy, ly)
-            zb, yb = zp.cpu().numpy().tobytes(), yp.cpu().numpy().tobytes()
-            ops.check_conv_status()       # the copies synchronised the stream: a flagged stream-K launch raises here, not a wrong file
-        head = MAGIC + struct.pack(self.HEAD, VERSION | (ARITH[m._precision] << 8), n, H, W, y.shape[-1], z.shape[-1], z.shape[1], z.shape[2], y.shape[1], y.shape[2],
-                                   sz, sy, lz, ly)
-        return head + zl.astype("<u4").tobytes() + yl.astype("<u4").tobytes() + zb + yb
+            return self.compress_latents(lat.uq[0].loc, lat.uq[1].loc, x.shape[1:3])
 
     def compress_many(self, xs):
         """``compress`` for several batches (e.g. one per image size of a set) -> their bitstreams, in order, byte for byte what one
         ``compress`` per batch returns.  The batches' transforms and entropy-coding launches run side by side on the library's
         side streams; the stream lengths of ALL batches come back in one copy, the packed payloads in another -- two host
-        synchronisations for the set instead of four per batch."""
+        synchronisations for the set instead of two per batch."""
         m = self.m
         xs = [m._as_device_images(x) for x in xs]
         if not xs:
@@ -423,39 +511,13 @@ class Codec:
                     st.wait_stream(main)
                 with torch.cuda.stream(st):
                     lat = m.infer_latent_rvs(x)
-                    z, y = lat.uq[0].loc, lat.uq[1].loc
-                    zi = round_to_int(z)
-                    hyper = m._hyper_synthesis(int_to_float(zi))
-                    _, _, sym = ops.entropy_scale_normal(y, hyper, want_symbols=True)
-                    sz, sy = _segments(zi[0].numel()), _segments(sym[0].numel())
-                    lz, ly = _lanes(-(-zi[0].numel() // sz)), _lanes(-(-sym[0].numel() // sy))
-                    zs, zlen = rans_encode_launch(zi, channel_table_ids(z.shape, m.device), self.z_tables, sz, lz)
-                    ys, ylen = rans_encode_launch(sym, scale_table_ids(hyper), self.y_tables, sy, ly)
-                jobs.append(dict(x=x, z=z, y=y, sz=sz, sy=sy, lz=lz, ly=ly, zs=zs, zlen=zlen, ys=ys, ylen=ylen, st=st))
+                    jobs.append(dict(self._launch_latents(lat.uq[0].loc, lat.uq[1].loc, x.shape[1:3]), st=st))
             for j in jobs:
                 if j["st"] is not main:
                     main.wait_stream(j["st"])
                     for t in (j["zs"], j["zlen"], j["ys"], j["ylen"]):
                         t.record_stream(main)
-            lens_h = torch.cat([t for j in jobs for t in (j["zlen"], j["ylen"])]).cpu().numpy().astype(np.int64)     # read-back 1 of 2
-            pays, o = [], 0
-            for j in jobs:
-                nz, ny = j["zlen"].numel(), j["ylen"].numel()
-                j["zl"], j["yl"] = lens_h[o:o + nz], lens_h[o + nz:o + nz + ny]
-                o += nz + ny
-                pays += [rans_encode_finish(j["zs"], j["zlen"], j["zl"]), rans_encode_finish(j["ys"], j["ylen"], j["yl"])]
-            words = torch.cat(pays).cpu().numpy()                                                                    # read-back 2 of 2
-            ops.check_conv_status()       # the copies synchronised the stream: a flagged stream-K launch raises here, not a wrong file
-        out, o = [], 0
-        for j in jobs:
-            n, H, W, _ = j["x"].shape
-            z, y = j["z"], j["y"]
-            zw, yw = int(j["zl"].sum()), int(j["yl"].sum())
-            head = MAGIC + struct.pack(self.HEAD, VERSION | (ARITH[m._precision] << 8), n, H, W, y.shape[-1], z.shape[-1], z.shape[1], z.shape[2],
-                                       y.shape[1], y.shape[2], j["sz"], j["sy"], j["lz"], j["ly"])
-            out.append(head + j["zl"].astype("<u4").tobytes() + j["yl"].astype("<u4").tobytes() + words[o:o + zw + yw].tobytes())
-            o += zw + yw
-        return out
+            return self._finish(jobs)
 
     def _parse(self, blob: bytes):
         """Header and stream lengths of one blob, checked against THIS model: nothing later trusts the header."""
@@ -688,10 +750,18 @@ class FactorizedCodec:
         h, w = m._analysis.out_hw(-(-H // f) * f, -(-W // f) * f)
         return (m._bottleneck_size, h, w)
 
-    def _launch(self, x):
-        """analysis -> the coder's launch(es) (``FUSED_CHANNEL_ENCODE``), on the current stream; no host synchronisation."""
-        m = self.m
-        y = m.infer_latent_rvs(x).uq[0].loc
+    def _check_latents(self, y, image_hw):
+        H, W = int(image_hw[0]), int(image_hw[1])
+        c, h, w = self.latent_shape(H, W)
+        n = y.shape[0]
+        if tuple(y.shape) != (n, h, w, c):
+            raise capi.SntcError(capi.ERR_BAD_SHAPE, f"latents {tuple(y.shape)} are not this model's for {n} images of {H} x {W}: {(n, h, w, c)}")
+        return n, H, W
+
+    def _launch_latents(self, y, image_hw):
+        """The coder's launch(es) (``FUSED_CHANNEL_ENCODE``) on latents of images of ``image_hw``, on the current stream; no host
+        synchronisation."""
+        n, H, W = self._check_latents(y, image_hw)
         e = y[0].numel()
         segments = _segments(e)
         lanes = _lanes(-(-e // segments))
@@ -699,22 +769,41 @@ class FactorizedCodec:
             scratch, lens, _ = rans_encode_channels_launch(y, self.y_tables, segments, lanes)
         else:
             scratch, lens = rans_encode_launch(round_to_int(y), channel_table_ids(y.shape, y.device), self.y_tables, segments, lanes)
-        return dict(x=x, y=y, segments=segments, lanes=lanes, scratch=scratch, lens=lens)
+        return dict(n=n, H=H, W=W, y=y, segments=segments, lanes=lanes, scratch=scratch, lens=lens)
+
+    def _launch(self, x):
+        """analysis -> ``_launch_latents``."""
+        return self._launch_latents(self.m.infer_latent_rvs(x).uq[0].loc, x.shape[1:3])
 
     def _blob(self, j, lens_h, words):
-        n, H, W, _ = j["x"].shape
         _, h, w, c = j["y"].shape
-        return pack_v4(ARITH[self.m._precision], n, H, W, c, h, w, j["segments"], j["lanes"], lens_h) + words.tobytes()
+        return pack_v4(ARITH[self.m._precision], j["n"], j["H"], j["W"], c, h, w, j["segments"], j["lanes"], lens_h) + words.tobytes()
+
+    def _finish_one(self, j):
+        lens_h = j["lens"].cpu().numpy().astype(np.int64)
+        words = rans_encode_finish(j["scratch"], j["lens"], lens_h).cpu().numpy()
+        ops.check_conv_status()       # the copies synchronised the stream: a flagged stream-K launch raises here, not a wrong file
+        return self._blob(j, lens_h, words)
+
+    def compress_latents(self, y_loc, image_hw) -> bytes:
+        """Latents of this model for images of ``image_hw`` = (H, W) -- the analysis', or ones refined by iterative inference --
+        -> the bitstream ``decompress`` reads.  ``compress(x)`` is this on ``infer_latent_rvs(x)``."""
+        with torch.cuda.device(self.m.device):
+            return self._finish_one(self._launch_latents(y_loc.contiguous(), image_hw))
+
+    def latents_cost(self, y_loc, x):
+        """``Codec.latents_cost`` for the one latent: -> (None, cost_y int64 [n] in 2^-16 bit, uint8 pixels, integer SSE [n])."""
+        n, H, W = self._check_latents(y_loc, x.shape[1:3])
+        yi = round_to_int(y_loc.contiguous())
+        cost_y = rans_cost(yi, channel_table_ids(yi.shape, yi.device), self.y_tables)
+        px, sse = self.m.decode(int_to_float(yi), None, (H, W), reference=x, check=False)
+        return None, cost_y, px, sse
 
     def compress(self, x) -> bytes:
         m = self.m
         x = m._as_device_images(x)
         with torch.cuda.device(m.device):
-            j = self._launch(x)
-            lens_h = j["lens"].cpu().numpy().astype(np.int64)
-            words = rans_encode_finish(j["scratch"], j["lens"], lens_h).cpu().numpy()
-            ops.check_conv_status()       # the copies synchronised the stream: a flagged stream-K launch raises here, not a wrong file
-        return self._blob(j, lens_h, words)
+            return self._finish_one(self._launch(x))
 
     def compress_many(self, xs):
         """``compress`` for several batches -> their bitstreams, in order, byte for byte what one ``compress`` per batch returns.

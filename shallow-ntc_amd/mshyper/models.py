@@ -623,9 +623,84 @@ class Model:
             self._codec = Codec(self)
         return self._codec
 
-    def compress(self, x) -> bytes:
-        """Images -> self-contained bitstream (rANS over the integer CDF tables of both entropy models)."""
-        return self._get_codec().compress(x)
+    def compress(self, x, itinf=None) -> bytes:
+        """Images -> self-contained bitstream (rANS over the integer CDF tables of both entropy models).
+        ``itinf`` = dict(steps, seed=0, check_every=None): refine the latents of THESE images by SGA iterative inference first
+        (``initialize_itinf`` + ``steps`` x ``itinf_train_step(x, seed=seed, fetch=False)`` under the model's own tau / learning-rate
+        schedules) and code, per image, the candidate with the smallest exact coded cost J (``coded_cost``) among the encoder's
+        own latents (step 0), every ``check_every``-th step if given, and the last step -- so the file is never worse, by J, than
+        that of ``compress(x)``.  ``last_compress_report`` then lists, per image, step_chosen, J_start, J_chosen, bits_start,
+        bits_chosen, and ``last_compress_latents`` holds what was coded.  Needs latent_config uq.method == 'sga' and precision
+        'fp32'; leaves the model in iterative-inference mode, as ``initialize_itinf`` does."""
+        if itinf is None:
+            return self._get_codec().compress(x)
+        return self._compress_itinf(x, **itinf)
+
+    def coded_cost(self, x, latent_rvs=None):
+        """Per image, the cost of what ``decompress`` will output for ``latent_rvs`` (None: the encoder's latents of x), without
+        writing a file: dict of float64 arrays [n] -- ``bits_z`` / ``bits_y`` = ``entropy_coding.rans_cost`` of the symbols the
+        file would carry (the coder's 16-bit integer tables, ESCAPE + 16 raw bits; the flushed lane states and the coder's
+        rounding slack, DESIGN.md 4.7, are not in it), ``bits`` their sum, ``sse`` the integer SSE of the decoded uint8 pixels,
+        ``D`` = the MSE of those pixels on the 0-255 scale (``distortion="ms_ssim"``: 1 - (MS-)SSIM of them, and ``msssim``),
+        ``J`` = bits / (H W) + ``lam`` * D with ``lam`` the scheduled rd_lambda.  One host read-back."""
+        x = self._as_device_images(x)
+        n, h, w, c = x.shape
+        ssim = self._distortion == "ms_ssim"
+        if ssim:
+            ops.msssim_scale_sizes(h, w)                              # ValueError before any launch
+        codec = self._get_codec()
+        with torch.cuda.device(self.device):
+            if latent_rvs is None:
+                latent_rvs = self.infer_latent_rvs(x)
+            cost_z, cost_y, px, sse = codec.latents_cost(*[rv.loc for rv in latent_rvs.uq], x)
+            rows = [torch.zeros_like(cost_y) if cost_z is None else cost_z, cost_y, sse]
+            parts = [torch.stack(rows).to(torch.float64).flatten()]   # integers below 2^53: exact
+            if ssim:
+                sums, counts, single = ops.image_quality_launch(ops.pixels_float(x, h, w), px.to(torch.float32), 255.0)
+                parts.append(sums.flatten())
+            host = torch.cat(parts).cpu().numpy()
+            ops.check_conv_status()
+        out = dict(bits_z=host[:n] / 65536.0, bits_y=host[n:2 * n] / 65536.0, sse=host[2 * n:3 * n], lam=float(self._scheduled_rd_lambda))
+        out["bits"] = out["bits_z"] + out["bits_y"]
+        out["D"] = out["sse"] / float(h * w * c)
+        if ssim:
+            out["msssim"] = ops.image_quality_finish(host[3 * n:].reshape(tuple(sums.shape)), counts, single)
+            out["D"] = 1.0 - out["msssim"]
+        out["J"] = out["bits"] / float(h * w) + out["lam"] * out["D"]
+        return out
+
+    def _compress_itinf(self, x, steps, seed=0, check_every=None):
+        if self._latent_config["uq"].get("method", "unoise") != "sga":       # every refusal before any launch
+            raise NotImplementedError("itinf_train_step implements latent_config uq.method == 'sga'")
+        if self._precision != "fp32":
+            raise NotImplementedError(f"compress(itinf=...) runs in precision 'fp32', not {self._precision!r}")
+        steps = int(steps)
+        if steps < 0 or (check_every is not None and int(check_every) < 1):
+            raise ValueError("compress(itinf=...): steps >= 0, check_every None or >= 1")
+        x = self._as_device_images(x)
+        n = x.shape[0]
+        if self._distortion == "ms_ssim":
+            ops.msssim_scale_sizes(x.shape[1], x.shape[2])
+        codec = self._get_codec()
+        self.initialize_itinf(x)
+        with torch.cuda.device(self.device):
+            start = self.coded_cost(x, self.latent_rvs)
+            best = [rv.loc.clone() for rv in self.latent_rvs.uq]
+            j_best, bits_best, step_best = start["J"].copy(), start["bits"].copy(), np.zeros(n, np.int64)
+            for done in range(1, steps + 1):
+                self.itinf_train_step(x, seed=seed, fetch=False)
+                if done != steps and (check_every is None or done % int(check_every)):
+                    continue
+                cand = self.coded_cost(x, self.latent_rvs)
+                for i in np.nonzero(cand["J"] < j_best)[0]:           # strictly better only: the encoder's latents win a tie
+                    for keep, rv in zip(best, self.latent_rvs.uq):
+                        keep[i].copy_(rv.loc[i])
+                    j_best[i], bits_best[i], step_best[i] = cand["J"][i], cand["bits"][i], done
+            blob = codec.compress_latents(*best, x.shape[1:3])
+        self.last_compress_latents = LatentRVCollection(uq=tuple(UQLatentRV(t) for t in best))
+        self.last_compress_report = [dict(step_chosen=int(step_best[i]), J_start=float(start["J"][i]), J_chosen=float(j_best[i]),
+                                          bits_start=float(start["bits"][i]), bits_chosen=float(bits_best[i])) for i in range(n)]
+        return blob
 
     def compress_many(self, xs):
         """Several batches (e.g. one per image size of a set) -> their bitstreams; the batches' launches run side by side and
