@@ -338,6 +338,37 @@ int sntc_conv_plan_tune(sntc_conv_plan* plan, const float* x, int n, int h, int 
 int sntc_conv_plan_candidates(const sntc_conv_plan* plan, int n, int h, int w, int* variants, int* stream_k, int capacity);
 int sntc_conv_plan_set_choice(sntc_conv_plan* plan, int n, int h, int w, int variant, int stream_k);
 int sntc_conv_plan_clear_tuning(sntc_conv_plan* plan);
+/* Forget the recorded choice of ONE call shape -- of the whole layer (ncols = 0) or of a column-limited launch (below) -- and keep
+ * every other one. */
+int sntc_conv_plan_drop_choice(sntc_conv_plan* plan, int n, int h, int w, int ncols);
+
+/* Column-limited launch: the layer restricted to its FIRST `ncols` output channels, y[n, ho, wo, ncols] compact.  A caller that
+ * needs only a leading slice of a layer's channels skips the rest of the contraction: the decoder reads mu = the first half of
+ * the hyper-synthesis' last layer and never its raw sigma (mshyper/models.py:278-279 splits the two; only the rate needs sigma).
+ * A single-group plan packs one weight row per output channel, in channel order, so the launch runs on the SAME plan and the same
+ * packed weights with fewer column tiles -- no second plan, no repacking -- and every output it computes is the same k-ordered
+ * fp32 fma chain (same split-K factor, same stream-K continuation) as in the whole layer: bit-identical to
+ * sntc_conv_forward's y[..., :ncols].
+ * Supported (sntc_conv_columns_supported -> 1): plans with one column group whose columns are the output channels (forward
+ * convolutions, stride-1 transposed ones), plain fp32 (not bf16 x 3, not row-packed), SNTC_EPI_STORE, 0 < ncols <= cout,
+ * ncols % 4 == 0; everything else returns SNTC_ERR_UNSUPPORTED before anything is launched.
+ * The queries and the measured-schedule calls below are their sntc_conv_* namesakes for such a launch: tiles, stream-K work
+ * units, workspace and candidates are all derived from `ncols`, and a choice recorded for one column count is never applied
+ * to another (nor to the whole layer).  Size the workspace with sntc_conv_columns_workspace_bytes for the same `ncols`. */
+int sntc_conv_columns_supported(const sntc_conv_plan* plan, int ncols);
+int sntc_conv_forward_columns(const sntc_conv_plan* plan, const float* x, int n, int h, int w, float* y, const float* res,
+                              const float* aux, void* workspace, size_t workspace_bytes, void* stream, int ncols);
+int64_t sntc_conv_columns_flops(const sntc_conv_plan* plan, int n, int h, int w, int ncols);
+int64_t sntc_conv_columns_workspace_bytes(const sntc_conv_plan* plan, int n, int h, int w, int ncols);
+/* variant / nblocks as sntc_conv_launch_info, column_major as sntc_conv_launch_order; any of the three may be NULL */
+int sntc_conv_columns_launch_info(const sntc_conv_plan* plan, int n, int h, int w, int ncols, int* variant, int* nblocks,
+                                  int* column_major);
+int64_t sntc_conv_columns_tune_workspace_bytes(const sntc_conv_plan* plan, int n, int h, int w, int ncols);
+int sntc_conv_columns_tune(sntc_conv_plan* plan, const float* x, int n, int h, int w, int ncols, float* y, void* workspace,
+                           size_t workspace_bytes, int reps, int* variant, int* stream_k, void* stream);
+int sntc_conv_columns_candidates(const sntc_conv_plan* plan, int n, int h, int w, int ncols, int* variants, int* stream_k,
+                                 int capacity);
+int sntc_conv_columns_set_choice(sntc_conv_plan* plan, int n, int h, int w, int ncols, int variant, int stream_k);
 
 /* ------------------------------------------------------------------------------------------
  * Small-channel GDN1 / IGDN1 (C <= 64): wave-shuffle contraction, no MFMA.
@@ -427,6 +458,10 @@ int sntc_entropy_scale_normal(const float* y, const float* hyper, int n, int64_t
 /* Decoder-side dequantisation: y_hat = symbols + mu  (mu = hyper[..., :C]). */
 int sntc_dequant_scale_normal(const int32_t* symbols, const float* hyper, int n, int64_t hw, int c,
                               float* y_hat, void* stream);
+/* The same from a mu tensor with `mu_stride` floats per pixel (>= c, a multiple of 4): c for the compact output of a mean-only
+ * hyper-synthesis (sntc_conv_forward_columns), 2 c for the full [mu | raw] rows. */
+int sntc_dequant_mean(const int32_t* symbols, const float* mu, int n, int64_t hw, int c, int mu_stride, float* y_hat,
+                      void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Bitstream: table-driven 64-way interleaved rANS, 16-bit quantised CDFs.  The reference has no

@@ -109,6 +109,18 @@ SIGNATURES = {
     "sntc_conv_plan_clear_tuning": (C.c_int, [_P]),
     "sntc_conv_plan_candidates": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     "sntc_conv_plan_set_choice": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sntc_conv_plan_drop_choice": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sntc_conv_columns_supported": (C.c_int, [_P, C.c_int]),
+    "sntc_conv_forward_columns": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_size_t, _P, C.c_int]),
+    "sntc_conv_columns_flops": (C.c_int64, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sntc_conv_columns_workspace_bytes": (C.c_int64, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sntc_conv_columns_launch_info": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                C.POINTER(C.c_int)]),
+    "sntc_conv_columns_tune_workspace_bytes": (C.c_int64, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sntc_conv_columns_tune": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int), _P]),
+    "sntc_conv_columns_candidates": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "sntc_conv_columns_set_choice": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sntc_gdn_small": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "sntc_two_layer_tail": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
                                       C.c_int, C.c_int, C.c_int, _P, _P]),
@@ -127,6 +139,7 @@ SIGNATURES = {
     "sntc_entropy_factorized": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, _P]),
     "sntc_entropy_scale_normal": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, C.c_int, _P]),
     "sntc_dequant_scale_normal": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, _P]),
+    "sntc_dequant_mean": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P]),
     "sntc_rans_cap_words": (C.c_int64, [C.c_int64, C.c_int]),
     "sntc_rans_encode": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int64, _P, _P, _P]),
     "sntc_rans_compact": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, _P, _P]),

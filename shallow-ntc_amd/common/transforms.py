@@ -140,6 +140,22 @@ class Transform:
     def _forward(self, x):
         return self._graph(x)
 
+    def leading_channels(self, x, ncols):
+        """The transform's first ``ncols`` output channels as a compact tensor, computed by a column-limited launch of its LAST
+        layer (ops.ConvPlan.columns: the same bits as ``self(x)[..., :ncols]``) -- or ``self(x)`` whole where that layer cannot
+        run one (several phase groups, split precision, another kernel) or ``ops.MEAN_ONLY_HYPER`` is off: look at the
+        result's channel count.  The decoder's hyper-synthesis: y_hat = symbols + mu never reads the raw-sigma half."""
+        if self._built_on != x.device:
+            self.build(x.shape[-1], x.device)
+        layers = self._graph.layers if isinstance(self._graph, Seq) else None
+        plan = getattr(layers[-1], "plan", None) if layers else None
+        if (not ops.MEAN_ONLY_HYPER or type(self)._forward is not Transform._forward or type(plan) is not ops.ConvPlan
+                or not plan.columns_supported(ncols)):
+            return self(x)
+        for l in layers[:-1]:
+            x = l(x)
+        return plan.columns(ncols)(x)
+
     def out_channels(self, input_channels=None):
         return self._graph.shapes(input_channels or self._cin)[1]
 

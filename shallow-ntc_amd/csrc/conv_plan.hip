@@ -161,7 +161,7 @@ struct sntc_conv_plan {
   // so a tuned entry changes the launch's speed and never its bits.  Guarded: plans are shared by concurrent streams / threads.
   struct Choice { int variant = 0; int sk = 0; };
   mutable std::mutex tune_mu;
-  std::map<std::array<int, 3>, Choice> tuned;
+  std::map<std::array<int, 4>, Choice> tuned;   // key (n, h, w, ncols): ncols = 0 the whole layer, else a column-limited launch
 };
 typedef sntc_conv_plan::Choice TuneChoice;
 
@@ -524,14 +524,16 @@ extern "C" int sntc_conv_out_shape(const sntc_conv_plan* p, int h, int w, int* h
   return SNTC_OK;
 }
 
-extern "C" int64_t sntc_conv_flops(const sntc_conv_plan* p, int n, int h, int w) {
+static int64_t conv_flops(const sntc_conv_plan* p, int n, int h, int w, int ncols) {
   if (!p) return 0;
   Geo g;
   if (geometry(p, h, w, &g)) return 0;
   const sntc_conv_desc& d = p->d;
   const int64_t px = p->up ? (int64_t)h * w : (int64_t)g.Ho * g.Wo;
-  return 2 * (int64_t)n * px * d.kh * d.kw * d.cin * d.cout;
+  return 2 * (int64_t)n * px * d.kh * d.kw * d.cin * (ncols > 0 ? ncols : d.cout);
 }
+
+extern "C" int64_t sntc_conv_flops(const sntc_conv_plan* p, int n, int h, int w) { return conv_flops(p, n, h, w, 0); }
 
 // Launch schedule of one call: the instance it runs (tile variant, loader, stage path, form), split-K factor, and whether the
 // persistent stream-K workers run it.
@@ -571,16 +573,51 @@ static int pick_ksplit(const sntc_conv_plan* p, const Geo& g) {
   return std::max(1, std::min({8, want, std::max(1, steps_min / 8)}));
 }
 
-static void count_work(const sntc_conv_plan* p, const GGInstance& inst, int64_t M, int64_t* tiles, int64_t* units, double* padded_macs) {
+// Column-limited launches (sntc_conv_forward_columns): a single-group plan outside phase mode packs column `col` = output channel
+// `col` (build_plan: cols[ch] = enc(0, 0, ch); pack_element reads d.w[... ch]), one weight row per column, so the first `ncols`
+// rows ARE the layer restricted to its first `ncols` output channels -- no second plan, no repacking.  `ncols` = 0 everywhere
+// below means the whole layer.
+static const char* columns_error(const sntc_conv_plan* p, int ncols) {
+  if (!p) return "null plan";
+  if (p->ngroups != 1 || p->phase_mode) return "column-limited launches: single-group plans whose columns are the output channels";
+  if (p->bf3 || p->s3 || p->rowpack) return "column-limited launches: plain fp32 plans only (not bf16 x 3, not row-packed)";
+  if (p->d.epilogue != SNTC_EPI_STORE) return "column-limited launches: plain store epilogue only";
+  if (ncols <= 0 || ncols > p->d.cout || (ncols & 3)) return "column-limited launches: 0 < ncols <= cout and ncols % 4 == 0";
+  return nullptr;
+}
+
+static inline int launch_cols(const sntc_conv_plan* p, int gi, int ncols) { return ncols > 0 ? ncols : p->g[gi].Ncol; }
+
+// Tiles and stream-K work units of a launch of `inst`'s tile shape over the first `ncols` columns.  THE one place they are
+// computed: the cost model, the workspace size, the tuning candidates and the launch arguments (GGGroup::ntn / tile0 / unit0,
+// GGArgs::tps / ups / units) all come from here, so the host-side stream-K partition and the kernel's own walk cannot disagree.
+struct Work {
+  int ntm = 0;
+  int ntn[kMaxGroups] = {};
+  int tile0[kMaxGroups] = {};         // tiles of the preceding groups inside one row strip
+  long long unit0[kMaxGroups] = {};   // units of the preceding groups inside one row strip
+  int tps = 0;                        // tiles / units per row strip, all groups
+  long long ups = 0;
+  int64_t tiles = 0, units = 0;
+  double padded_macs = 0;
+};
+
+static Work work_of(const sntc_conv_plan* p, const GGInstance& inst, int64_t M, int ncols) {
+  Work wk;
   const int bm = inst.bm, bn = inst.bn;
-  const int64_t ntm = (M + bm - 1) / bm;
-  *tiles = 0; *units = 0; *padded_macs = 0;
+  wk.ntm = (int)((M + bm - 1) / bm);
   for (int gi = 0; gi < p->ngroups; ++gi) {
-    const int64_t ntn = (p->g[gi].Ncol + bn - 1) / bn;
-    *tiles += ntn * ntm;
-    *units += ntn * ntm * (p->g[gi].K / kStage);
-    *padded_macs += (double)p->g[gi].K * (double)(ntn * bn) * (double)(ntm * bm);
+    const int steps = p->g[gi].K / kStage;
+    wk.ntn[gi] = (launch_cols(p, gi, ncols) + bn - 1) / bn;
+    wk.tile0[gi] = wk.tps;
+    wk.unit0[gi] = wk.ups;
+    wk.tps += wk.ntn[gi];
+    wk.ups += (long long)wk.ntn[gi] * steps;
+    wk.padded_macs += (double)p->g[gi].K * (double)((int64_t)wk.ntn[gi] * bn) * (double)((int64_t)wk.ntm * bm);
   }
+  wk.tiles = (int64_t)wk.tps * wk.ntm;
+  wk.units = (int64_t)wk.ups * wk.ntm;
+  return wk;
 }
 
 // Tile variant: least padded multiply-adds x (rounds of resident workgroups actually run / rounds of work) -- the second
@@ -606,9 +643,9 @@ static Sched schedule_s3(const sntc_conv_plan* p, const Geo& g, int64_t n, const
     const GGInstance* inst = gg_find(v, kLoadVec, kStageDma, kFormPresplit);
     if (!inst) continue;
     const int cus = std::max(8, gg_resident(*inst));
-    int64_t tiles, units;
-    double macs;
-    count_work(p, *inst, M, &tiles, &units, &macs);
+    const Work wk = work_of(p, *inst, M, 0);
+    const int64_t tiles = wk.tiles, units = wk.units;
+    const double macs = wk.padded_macs;
     Sched s;
     s.inst = inst;
     s.ksplit = 1;
@@ -648,20 +685,23 @@ static Sched schedule_s3(const sntc_conv_plan* p, const Geo& g, int64_t n, const
 // fp32 stream-K unit order of a launch: column tile outermost (the COLM twin) for single-group plans whose packed weights do not
 // fit an XCD's 4 MB L2 -- the 3x3 hyper-synthesis layer (11 MB): HBM-side reads of the launch 1667 -> 857 MB.  The twin replaces
 // the strip-major 128 x 128 register-staged vector instance only where it keeps as many workgroups resident: the workers were
-// counted from that instance's residency.
-static const GGInstance* column_major(const sntc_conv_plan* p, const Sched& sc) {
+// counted from that instance's residency.  A column-limited launch reads only its own rows: the rule looks at those.
+static const GGInstance* column_major(const sntc_conv_plan* p, const Sched& sc, int ncols) {
   const GGInstance* strip = sc.inst;
   if (!sc.sk || strip->load != kLoadVec || strip->stage != kStageRing || strip->form != kFormPlain || p->ngroups != 1 || p->colm == 0 ||
-      (p->colm != 1 && (size_t)p->g[0].Ncol * p->g[0].K * sizeof(float) <= ((size_t)4 << 20)))
+      (p->colm != 1 && (size_t)launch_cols(p, 0, ncols) * p->g[0].K * sizeof(float) <= ((size_t)4 << 20)))
     return nullptr;
   const GGInstance* twin = gg_find(strip->variant, kLoadVec, kStageRing, kFormColm);
   return twin && gg_resident(*twin) >= gg_resident(*strip) ? twin : nullptr;
 }
 
-static Sched schedule(const sntc_conv_plan* p, const Geo& g, int64_t n, bool fused = false, const TuneChoice* force = nullptr) {
+static Sched schedule(const sntc_conv_plan* p, const Geo& g, int64_t n, bool fused = false, const TuneChoice* force = nullptr,
+                      int ncols = 0) {
   if (p->s3) return schedule_s3(p, g, n, force);
   Sched best;
   const int64_t M = n * g.Qh * g.Qw;
+  // (the split-K factor stays the LAYER's, whatever the column count: a column-limited launch then sums each output's K ranges
+  // exactly as the whole layer does -- the same bits)
   const int ksplit = fused ? 1 : pick_ksplit(p, g);
   const int msteps = max_steps(p);
   const bool pro = p->d.prologue != SNTC_PRO_NONE;
@@ -680,9 +720,9 @@ static Sched schedule(const sntc_conv_plan* p, const Geo& g, int64_t n, bool fus
     const GGInstance* ring = gg_find(v, load, kStageRing, form);
     if (!ring) continue;
     const GGInstance* dma = !fused && plan_dma(p) ? gg_find(v, load, kStageDma, kFormPlain) : nullptr;
-    int64_t tiles, units;
-    double macs;
-    count_work(p, *ring, M, &tiles, &units, &macs);
+    const Work wk = work_of(p, *ring, M, ncols);
+    const int64_t tiles = wk.tiles, units = wk.units;
+    const double macs = wk.padded_macs;
     Sched s;
     s.inst = dma ? dma : ring;
     const int resident = std::max(1, gg_resident(*s.inst));
@@ -738,19 +778,19 @@ static Sched schedule(const sntc_conv_plan* p, const Geo& g, int64_t n, bool fus
 #endif
     if (cost < best_cost) { best_cost = cost; best = s; }
   }
-  if (const GGInstance* twin = column_major(p, best)) best.inst = twin;
+  if (const GGInstance* twin = column_major(p, best, ncols)) best.inst = twin;
   return best;
 }
 
 // The schedule of a call: the measured choice for this (n, h, w) if sntc_conv_plan_tune recorded one -- unless the plan's tile or
 // schedule is forced (tests, profiling) -- else the cost model's.
-static Sched plan_schedule(const sntc_conv_plan* p, const Geo& g, int n, int h, int w, bool fused = false) {
+static Sched plan_schedule(const sntc_conv_plan* p, const Geo& g, int n, int h, int w, bool fused = false, int ncols = 0) {
   if (!fused && p->tile == 0 && !p->no_stream_k && !p->force_stream_k) {
     TuneChoice c;
     bool have = false;
     {
       std::lock_guard<std::mutex> lk(p->tune_mu);
-      auto it = p->tuned.find({n, h, w});
+      auto it = p->tuned.find({n, h, w, ncols});   // a choice measured at one width is never applied at another
       if (it != p->tuned.end()) { c = it->second; have = true; }
     }
     // a measured stream-K choice says nothing about the static schedules: with stream-K switched off process-wide
@@ -758,55 +798,61 @@ static Sched plan_schedule(const sntc_conv_plan* p, const Geo& g, int n, int h, 
     // among the static candidates instead of running the stream-K tile one workgroup per tile
     if (have && c.sk != 0 && !g_stream_k_enabled.load(std::memory_order_relaxed)) have = false;
     if (have) {
-      const Sched s = schedule(p, g, n, false, &c);
+      const Sched s = schedule(p, g, n, false, &c, ncols);
       if (s.inst) return s;
     }
   }
-  return schedule(p, g, n, fused);
+  return schedule(p, g, n, fused, nullptr, ncols);
 }
 
-static int64_t workspace_floats(const sntc_conv_plan* p, int64_t M, const Sched& s) {
+static int64_t workspace_floats(const sntc_conv_plan* p, int64_t M, const Sched& s, int ncols = 0) {
   if (s.sk)      // slabs + one flag per worker
     return (int64_t)s.workers * (int64_t)s.inst->slab_floats + s.workers;
   if (s.ksplit <= 1) return 0;
   int64_t cols = 0;
-  for (int gi = 0; gi < p->ngroups; ++gi) cols += p->g[gi].Ncol;
+  for (int gi = 0; gi < p->ngroups; ++gi) cols += launch_cols(p, gi, ncols);
   return (int64_t)s.ksplit * M * cols;
 }
 
-extern "C" int64_t sntc_conv_workspace_bytes(const sntc_conv_plan* p, int n, int h, int w) {
+static int64_t conv_workspace_bytes(const sntc_conv_plan* p, int n, int h, int w, int ncols) {
   if (!p) return 0;
   Geo g;
   if (geometry(p, h, w, &g)) return 0;
-  return 4 * workspace_floats(p, (int64_t)n * g.Qh * g.Qw, plan_schedule(p, g, n, h, w));
+  return 4 * workspace_floats(p, (int64_t)n * g.Qh * g.Qw, plan_schedule(p, g, n, h, w, false, ncols), ncols);
+}
+
+extern "C" int64_t sntc_conv_workspace_bytes(const sntc_conv_plan* p, int n, int h, int w) { return conv_workspace_bytes(p, n, h, w, 0); }
+
+static int conv_launch_info(const sntc_conv_plan* p, int n, int h, int w, int ncols, int* variant, int* nblocks, int* column_major_out) {
+  Geo g;
+  int rc = geometry(p, h, w, &g);
+  if (rc) return rc;
+  const Sched s = plan_schedule(p, g, n, h, w, false, ncols);
+  if (variant) *variant = s.inst ? s.inst->variant : 0;
+  if (nblocks) *nblocks = (int)s.blocks;
+  if (column_major_out) *column_major_out = s.inst && s.inst->form == kFormColm ? 1 : 0;
+  return SNTC_OK;
 }
 
 extern "C" int sntc_conv_launch_order(const sntc_conv_plan* p, int n, int h, int w, int* column_major_out) {
   if (!p || !column_major_out) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_launch_order: null argument");
-  Geo g;
-  int rc = geometry(p, h, w, &g);
-  if (rc) return rc;
-  const Sched s = plan_schedule(p, g, n, h, w);
-  *column_major_out = s.inst && s.inst->form == kFormColm ? 1 : 0;
-  return SNTC_OK;
+  return conv_launch_info(p, n, h, w, 0, nullptr, nullptr, column_major_out);
 }
 
 extern "C" int sntc_conv_launch_info(const sntc_conv_plan* p, int n, int h, int w, int* variant, int* nblocks) {
   if (!p || !variant || !nblocks) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_launch_info: null argument");
-  Geo g;
-  int rc = geometry(p, h, w, &g);
-  if (rc) return rc;
-  const Sched s = plan_schedule(p, g, n, h, w);
-  *variant = s.inst ? s.inst->variant : 0;
-  *nblocks = (int)s.blocks;
-  return SNTC_OK;
+  return conv_launch_info(p, n, h, w, 0, variant, nblocks, nullptr);
 }
 
 // One launch of plan p; with p2 (validated by sntc_conv_forward_fused) the 1x1 plan p2 runs behind p inside the same launch.
 static int conv_forward_impl(const sntc_conv_plan* p, const sntc_conv_plan* p2, const float* x, int n, int h, int w, float* y,
                              const float* res, const float* aux, void* workspace, size_t workspace_bytes, void* stream,
-                             const TuneChoice* force = nullptr) {
+                             const TuneChoice* force = nullptr, int ncols = 0) {
   if (!p || !x || !y) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_forward: null argument");
+  if (ncols != 0) {      // column-limited launch: refused here, before anything is scheduled or launched
+    if (const char* why = columns_error(p, ncols)) return fail(SNTC_ERR_UNSUPPORTED, why);
+    if (p2) return fail(SNTC_ERR_UNSUPPORTED, "column-limited launches: not the fused pair");
+  }
   if (n < 1) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_forward: empty batch");
   const sntc_conv_desc& d = p->d;
   const int epilogue = p2 ? p2->d.epilogue : d.epilogue;
@@ -820,13 +866,17 @@ static int conv_forward_impl(const sntc_conv_plan* p, const sntc_conv_plan* p2, 
   if (M > 0x7fffffffLL || x_bytes >= (1LL << 31))
     return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_forward: input tensor must be < 2 GiB (32-bit buffer offsets); split the batch");
   if (p2 && M * p2->d.cout >= (1LL << 32)) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_forward_fused: output too large; split the batch");
-  const Sched sc = force ? schedule(p, g, n, false, force) : plan_schedule(p, g, n, h, w, p2 != nullptr);
+  const Sched sc = force ? schedule(p, g, n, false, force, ncols) : plan_schedule(p, g, n, h, w, p2 != nullptr, ncols);
   if (!sc.inst) return fail(SNTC_ERR_UNSUPPORTED, "sntc_conv_forward: no compiled instance for this plan and tile variant");
-  const int64_t ws_floats = workspace_floats(p, M, sc);
+  const int64_t ws_floats = workspace_floats(p, M, sc, ncols);
   if (ws_floats > 0 && (!workspace || workspace_bytes < (size_t)ws_floats * 4))
     return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_forward: this call needs sntc_conv_workspace_bytes() of workspace "
                                     "(split-K slabs / stream-K hand-off)");
   const GGInstance& inst = *sc.inst;
+  // the launch's tiles and units, from the helper the schedule counted its workers with: a stream-K worker whose share was cut
+  // from another unit count than the kernel walks would wait for a hand-off that never comes
+  const Work wk = work_of(p, inst, M, ncols);
+  if (sc.sk && wk.units != sc.units) return fail(SNTC_ERR_HIP, "sntc_conv_forward: schedule and launch disagree about the work units");
   GGArgs a{};
   a.ksplit = sc.ksplit;
   a.slab = static_cast<float*>(workspace);
@@ -834,44 +884,43 @@ static int conv_forward_impl(const sntc_conv_plan* p, const sntc_conv_plan* p2, 
   a.x_bytes = (unsigned)x_bytes;
   a.N = n; a.H = h; a.W = w; a.Cin = d.cin;
   a.Qh = g.Qh; a.Qw = g.Qw; a.M = (int)M;
-  a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = d.cout;
+  a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = ncols > 0 ? ncols : d.cout;      // the output's row stride: a column-limited launch writes compact rows
   a.sA = g.sA; a.tstep = g.tstep; a.offy = g.offy; a.offx = g.offx; a.sO = g.sO;
   a.act = d.act; a.epi = epilogue; a.pro = d.prologue;
-  a.ntm = (int)((M + inst.bm - 1) / inst.bm);
+  a.ntm = wk.ntm;
   a.ngroups = p->ngroups;
   if (p2) { a.w2f = p2->w2f; a.bias2 = p2->bias; a.Cout2 = p2->d.cout; }
   a.status = gg_status_word();
   if (!a.status) return fail(SNTC_ERR_HIP, "sntc_conv_forward: the device tables of the current device are not initialised");
   a.sk = sc.sk ? 1 : 0;
   a.nworkers = sc.workers;
-  a.units = sc.units;
+  a.units = wk.units;
   if (sc.sk) {
     a.sk_slab = static_cast<float*>(workspace);
     a.sk_flags = reinterpret_cast<int*>(a.sk_slab + (size_t)sc.workers * inst.slab_floats);
     a.slab = nullptr;
     if (int zrc = zero_async(a.sk_flags, sizeof(int) * sc.workers, (hipStream_t)stream)) return zrc;
   }
-  int nb = 0, tile0 = 0;
-  long long unit0 = 0;
+  int nb = 0;
   size_t slab_off = 0;
   for (int gi = 0; gi < p->ngroups; ++gi) {
     GGGroup& G = a.g[gi];
     G.wp = p->g[gi].wp; G.taps = p->g[gi].taps; G.cols = reinterpret_cast<const int*>(p->g[gi].cols);
-    G.T = p->g[gi].T; G.K = p->g[gi].K; G.Ncol = p->g[gi].Ncol; G.tw = p->g[gi].tw;
-    G.ntn = (G.Ncol + inst.bn - 1) / inst.bn;
+    // Ncol bounds the kernel's weight descriptor, its "rows past Ncol re-read the last column" clamp and the epilogue's column
+    // test: with the limited count the launch neither reads nor writes a column past it
+    G.T = p->g[gi].T; G.K = p->g[gi].K; G.Ncol = launch_cols(p, gi, ncols); G.tw = p->g[gi].tw;
+    G.ntn = wk.ntn[gi];
     G.steps = G.K / kStage;
     G.blk0 = nb;
-    G.tile0 = tile0;
-    G.unit0 = unit0;
+    G.tile0 = wk.tile0[gi];
+    G.unit0 = wk.unit0[gi];
     nb += G.ntn * a.ntm * sc.ksplit;
-    tile0 += G.ntn;
-    unit0 += (long long)G.ntn * G.steps;
     G.slab_off = slab_off;
     G.q0y = p->g[gi].q0y; G.q0x = p->g[gi].q0x;
     slab_off += (size_t)sc.ksplit * M * G.Ncol;
   }
-  a.tps = tile0;
-  a.ups = (int)unit0;
+  a.tps = wk.tps;
+  a.ups = (int)wk.ups;
   // pre-split stream-K unit order: strip-major, as the fp32 kernel (every worker's share mixes the phase groups; with the column
   // tile outermost the last workers of the 13x13/8 synthesis get nothing but 20-stage tiles: 0.55 against 0.45 ms).  The
   // column-major order stays selectable for the A/B: sntc_conv_plan_set_schedule's stage-path bit ("off") doubles as the switch
@@ -893,41 +942,47 @@ extern "C" int sntc_conv_forward(const sntc_conv_plan* p, const float* x, int n,
 // one runs is a question of speed only.  The cost model of schedule() ranks them from tile counts; this measures them on the
 // caller's buffers, for one (n, h, w), and records the winner in the plan.  Split-K factors are not candidates (they are a
 // function of the layer and the per-image geometry only, by contract).
-static void tune_candidates(const sntc_conv_plan* p, const Geo& g, int n, std::vector<std::pair<TuneChoice, Sched>>* out) {
+static void tune_candidates(const sntc_conv_plan* p, const Geo& g, int n, std::vector<std::pair<TuneChoice, Sched>>* out, int ncols = 0) {
   for (int v = 1; v <= kMaxVariant; ++v) {
     if (!base_instance(p, v)) continue;
     for (int sk = 1; sk >= 0; --sk) {
       TuneChoice c;
       c.variant = v;
       c.sk = sk;
-      const Sched s = schedule(p, g, n, false, &c);
+      const Sched s = schedule(p, g, n, false, &c, ncols);
       if (!s.inst || s.inst->variant != v || (sk && !s.sk)) continue;
       out->push_back({c, s});
     }
   }
 }
 
-extern "C" int64_t sntc_conv_tune_workspace_bytes(const sntc_conv_plan* p, int n, int h, int w) {
+static int64_t conv_tune_workspace_bytes(const sntc_conv_plan* p, int n, int h, int w, int ncols) {
   if (!p) return 0;
   Geo g;
   if (geometry(p, h, w, &g)) return 0;
   std::vector<std::pair<TuneChoice, Sched>> cand;
-  tune_candidates(p, g, n, &cand);
+  tune_candidates(p, g, n, &cand, ncols);
   int64_t m = 0;
-  for (auto& c : cand) m = std::max(m, workspace_floats(p, (int64_t)n * g.Qh * g.Qw, c.second));
+  for (auto& c : cand) m = std::max(m, workspace_floats(p, (int64_t)n * g.Qh * g.Qw, c.second, ncols));
   return 4 * m;
 }
 
-extern "C" int sntc_conv_plan_tune(sntc_conv_plan* p, const float* x, int n, int h, int w, float* y, const float* res,
-                                   const float* aux, void* workspace, size_t workspace_bytes, int reps, int* variant,
-                                   int* stream_k, void* stream) {
+extern "C" int64_t sntc_conv_tune_workspace_bytes(const sntc_conv_plan* p, int n, int h, int w) {
+  return conv_tune_workspace_bytes(p, n, h, w, 0);
+}
+
+static int conv_plan_tune(sntc_conv_plan* p, const float* x, int n, int h, int w, int ncols, float* y, const float* res,
+                          const float* aux, void* workspace, size_t workspace_bytes, int reps, int* variant,
+                          int* stream_k, void* stream) {
   if (!p || !x || !y) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_plan_tune: null argument");
+  if (ncols != 0)
+    if (const char* why = columns_error(p, ncols)) return fail(SNTC_ERR_UNSUPPORTED, why);
   Geo g;
   int rc = geometry(p, h, w, &g);
   if (rc) return rc;
   reps = std::max(1, std::min(reps, 100));
   std::vector<std::pair<TuneChoice, Sched>> cand;
-  tune_candidates(p, g, n, &cand);
+  tune_candidates(p, g, n, &cand, ncols);
   if (cand.empty()) return fail(SNTC_ERR_UNSUPPORTED, "sntc_conv_plan_tune: no candidate");
   hipEvent_t e0, e1;
   SNTC_HIP(hipEventCreate(&e0));
@@ -935,12 +990,12 @@ extern "C" int sntc_conv_plan_tune(sntc_conv_plan* p, const float* x, int n, int
   float best_ms = 1e30f;
   TuneChoice best;
   for (auto& c : cand) {
-    if ((size_t)(4 * workspace_floats(p, (int64_t)n * g.Qh * g.Qw, c.second)) > workspace_bytes) continue;
-    rc = conv_forward_impl(p, nullptr, x, n, h, w, y, res, aux, workspace, workspace_bytes, stream, &c.first);      // warm
+    if ((size_t)(4 * workspace_floats(p, (int64_t)n * g.Qh * g.Qw, c.second, ncols)) > workspace_bytes) continue;
+    rc = conv_forward_impl(p, nullptr, x, n, h, w, y, res, aux, workspace, workspace_bytes, stream, &c.first, ncols);      // warm
     if (rc) break;
     (void)hipEventRecord(e0, (hipStream_t)stream);
     for (int r = 0; r < reps && !rc; ++r)
-      rc = conv_forward_impl(p, nullptr, x, n, h, w, y, res, aux, workspace, workspace_bytes, stream, &c.first);
+      rc = conv_forward_impl(p, nullptr, x, n, h, w, y, res, aux, workspace, workspace_bytes, stream, &c.first, ncols);
     (void)hipEventRecord(e1, (hipStream_t)stream);
     if (rc) break;
     float ms = 0.f;
@@ -953,7 +1008,7 @@ extern "C" int sntc_conv_plan_tune(sntc_conv_plan* p, const float* x, int n, int
   if (best.variant == 0) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_plan_tune: workspace smaller than sntc_conv_tune_workspace_bytes()");
   {
     std::lock_guard<std::mutex> lk(p->tune_mu);
-    p->tuned[{n, h, w}] = best;
+    p->tuned[{n, h, w, ncols}] = best;
   }
   if (variant) *variant = best.variant;
   if (stream_k) *stream_k = best.sk;
@@ -961,32 +1016,104 @@ extern "C" int sntc_conv_plan_tune(sntc_conv_plan* p, const float* x, int n, int
   return SNTC_OK;
 }
 
-extern "C" int sntc_conv_plan_set_choice(sntc_conv_plan* p, int n, int h, int w, int variant, int stream_k) {
+extern "C" int sntc_conv_plan_tune(sntc_conv_plan* p, const float* x, int n, int h, int w, float* y, const float* res,
+                                   const float* aux, void* workspace, size_t workspace_bytes, int reps, int* variant,
+                                   int* stream_k, void* stream) {
+  return conv_plan_tune(p, x, n, h, w, 0, y, res, aux, workspace, workspace_bytes, reps, variant, stream_k, stream);
+}
+
+static int conv_plan_set_choice(sntc_conv_plan* p, int n, int h, int w, int ncols, int variant, int stream_k) {
   if (!p) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_plan_set_choice: null plan");
+  if (ncols != 0)
+    if (const char* why = columns_error(p, ncols)) return fail(SNTC_ERR_UNSUPPORTED, why);
   Geo g;
   int rc = geometry(p, h, w, &g);
   if (rc) return rc;
   TuneChoice c;
   c.variant = variant;
   c.sk = stream_k ? 1 : 0;
-  const Sched s = schedule(p, g, n, false, &c);
+  const Sched s = schedule(p, g, n, false, &c, ncols);
   if (!s.inst || s.inst->variant != variant || (stream_k && !s.sk))
     return fail(SNTC_ERR_UNSUPPORTED, "sntc_conv_plan_set_choice: not a candidate of this plan for this call shape");
   std::lock_guard<std::mutex> lk(p->tune_mu);
-  p->tuned[{n, h, w}] = c;
+  p->tuned[{n, h, w, ncols}] = c;
   return SNTC_OK;
 }
 
-extern "C" int sntc_conv_plan_candidates(const sntc_conv_plan* p, int n, int h, int w, int* variants, int* stream_k, int capacity) {
+extern "C" int sntc_conv_plan_set_choice(sntc_conv_plan* p, int n, int h, int w, int variant, int stream_k) {
+  return conv_plan_set_choice(p, n, h, w, 0, variant, stream_k);
+}
+
+static int conv_plan_candidates(const sntc_conv_plan* p, int n, int h, int w, int ncols, int* variants, int* stream_k, int capacity) {
   if (!p || !variants || !stream_k || capacity < 1) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_plan_candidates: bad argument");
+  if (ncols != 0 && columns_error(p, ncols)) { (void)fail(SNTC_ERR_UNSUPPORTED, columns_error(p, ncols)); return -1; }
   Geo g;
   if (geometry(p, h, w, &g)) return -1;
   std::vector<std::pair<TuneChoice, Sched>> cand;
-  tune_candidates(p, g, n, &cand);
+  tune_candidates(p, g, n, &cand, ncols);
   int k = 0;
   for (auto& c : cand)
     if (k < capacity) { variants[k] = c.first.variant; stream_k[k] = c.first.sk; ++k; }
   return k;
+}
+
+extern "C" int sntc_conv_plan_candidates(const sntc_conv_plan* p, int n, int h, int w, int* variants, int* stream_k, int capacity) {
+  return conv_plan_candidates(p, n, h, w, 0, variants, stream_k, capacity);
+}
+
+// ---- column-limited launches: the sntc_conv_* calls above with one more argument, `ncols` -- the layer restricted to its
+// first `ncols` output channels, written as a compact [n, Ho, Wo, ncols] tensor.  Same plan, same packed weights, same kernels:
+// the launch simply has fewer column tiles, and every output it does compute is the same k-ordered chain as in the whole layer.
+extern "C" int sntc_conv_columns_supported(const sntc_conv_plan* p, int ncols) { return columns_error(p, ncols) ? 0 : 1; }
+
+extern "C" int sntc_conv_forward_columns(const sntc_conv_plan* p, const float* x, int n, int h, int w, float* y, const float* res,
+                                         const float* aux, void* workspace, size_t workspace_bytes, void* stream, int ncols) {
+  if (const char* why = columns_error(p, ncols)) return fail(SNTC_ERR_UNSUPPORTED, why);
+  return conv_forward_impl(p, nullptr, x, n, h, w, y, res, aux, workspace, workspace_bytes, stream, nullptr, ncols);
+}
+
+extern "C" int64_t sntc_conv_columns_flops(const sntc_conv_plan* p, int n, int h, int w, int ncols) {
+  return columns_error(p, ncols) ? 0 : conv_flops(p, n, h, w, ncols);
+}
+
+extern "C" int64_t sntc_conv_columns_workspace_bytes(const sntc_conv_plan* p, int n, int h, int w, int ncols) {
+  return columns_error(p, ncols) ? 0 : conv_workspace_bytes(p, n, h, w, ncols);
+}
+
+extern "C" int sntc_conv_columns_launch_info(const sntc_conv_plan* p, int n, int h, int w, int ncols, int* variant, int* nblocks,
+                                             int* column_major_out) {
+  if (const char* why = columns_error(p, ncols)) return fail(SNTC_ERR_UNSUPPORTED, why);
+  return conv_launch_info(p, n, h, w, ncols, variant, nblocks, column_major_out);
+}
+
+extern "C" int64_t sntc_conv_columns_tune_workspace_bytes(const sntc_conv_plan* p, int n, int h, int w, int ncols) {
+  return columns_error(p, ncols) ? 0 : conv_tune_workspace_bytes(p, n, h, w, ncols);
+}
+
+extern "C" int sntc_conv_columns_tune(sntc_conv_plan* p, const float* x, int n, int h, int w, int ncols, float* y, void* workspace,
+                                      size_t workspace_bytes, int reps, int* variant, int* stream_k, void* stream) {
+  if (const char* why = columns_error(p, ncols)) return fail(SNTC_ERR_UNSUPPORTED, why);
+  return conv_plan_tune(p, x, n, h, w, ncols, y, nullptr, nullptr, workspace, workspace_bytes, reps, variant, stream_k, stream);
+}
+
+extern "C" int sntc_conv_columns_candidates(const sntc_conv_plan* p, int n, int h, int w, int ncols, int* variants, int* stream_k,
+                                            int capacity) {
+  if (columns_error(p, ncols)) { (void)fail(SNTC_ERR_UNSUPPORTED, columns_error(p, ncols)); return -1; }
+  return conv_plan_candidates(p, n, h, w, ncols, variants, stream_k, capacity);
+}
+
+extern "C" int sntc_conv_columns_set_choice(sntc_conv_plan* p, int n, int h, int w, int ncols, int variant, int stream_k) {
+  if (const char* why = columns_error(p, ncols)) return fail(SNTC_ERR_UNSUPPORTED, why);
+  return conv_plan_set_choice(p, n, h, w, ncols, variant, stream_k);
+}
+
+// Forget ONE recorded choice -- (n, h, w) of the whole layer (ncols = 0) or of a column-limited launch -- and leave the others:
+// the whole layer and its column-limited launches keep their choices in one plan.
+extern "C" int sntc_conv_plan_drop_choice(sntc_conv_plan* p, int n, int h, int w, int ncols) {
+  if (!p) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_plan_drop_choice: null plan");
+  std::lock_guard<std::mutex> lk(p->tune_mu);
+  p->tuned.erase({n, h, w, ncols});
+  return SNTC_OK;
 }
 
 extern "C" int sntc_conv_plan_clear_tuning(sntc_conv_plan* p) {

@@ -136,15 +136,17 @@ __global__ void __launch_bounds__(256) scale_normal_kernel(const float* __restri
   block_sum_to(acc, bits + img);
 }
 
+// `hstride`: floats per pixel of `hyper` -- 2 c for the hyper-synthesis' [mu | raw sigma] rows, c for a compact mu (the mean-only
+// hyper-synthesis of the decoder, sntc_dequant_mean)
 __global__ void __launch_bounds__(256) dequant_kernel(const int32_t* __restrict__ symbols, const float* __restrict__ hyper,
-                                                      int64_t npix, int c, float* __restrict__ y_hat) {
+                                                      int64_t npix, int c, int hstride, float* __restrict__ y_hat) {
   const int c4 = c >> 2;
   const int64_t nvec = npix * c4;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t p = i / c4;
     const int ch = (int)(i - p * c4) << 2;
     const i32x4 s = *reinterpret_cast<const i32x4*>(symbols + p * c + ch);
-    const f32x4 mu = *reinterpret_cast<const f32x4*>(hyper + p * 2 * c + ch);
+    const f32x4 mu = *reinterpret_cast<const f32x4*>(hyper + p * hstride + ch);
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = (float)s[e] + mu[e];
@@ -428,7 +430,19 @@ extern "C" int sntc_dequant_scale_normal(const int32_t* symbols, const float* hy
   if (n < 1 || hw < 1 || c < 1 || (c % 4)) return fail(SNTC_ERR_BAD_SHAPE, "sntc_dequant_scale_normal: bad sizes");
   const int64_t npix = (int64_t)n * hw;
   hipLaunchKernelGGL(dequant_kernel, dim3(grid_for(npix * c / 4)), dim3(256), 0, (hipStream_t)stream, symbols, hyper,
-                     npix, c, y_hat);
+                     npix, c, 2 * c, y_hat);
+  SNTC_HIP(hipGetLastError());
+  return SNTC_OK;
+}
+
+extern "C" int sntc_dequant_mean(const int32_t* symbols, const float* mu, int n, int64_t hw, int c, int mu_stride, float* y_hat,
+                                 void* stream) {
+  if (!symbols || !mu || !y_hat) return fail(SNTC_ERR_BAD_SHAPE, "sntc_dequant_mean: null argument");
+  if (n < 1 || hw < 1 || c < 1 || (c % 4) || mu_stride < c || (mu_stride % 4))
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_dequant_mean: bad sizes (c % 4 == 0, mu_stride >= c, mu_stride % 4 == 0)");
+  const int64_t npix = (int64_t)n * hw;
+  hipLaunchKernelGGL(dequant_kernel, dim3(grid_for(npix * c / 4)), dim3(256), 0, (hipStream_t)stream, symbols, mu,
+                     npix, c, mu_stride, y_hat);
   SNTC_HIP(hipGetLastError());
   return SNTC_OK;
 }

@@ -550,11 +550,10 @@ class Model:
         """(z_hat, symbols) -> hyper-synthesis -> y_hat = symbols + mu -> synthesis -> uint8 pixels
         [n, H, W, 3] (and the per-image integer SSE against ``reference`` if given).  ``check`` as in ``encode``."""
         with torch.cuda.device(self.device):
-            hyper = self._hyper_synthesis(z_hat)
             if self._synthesis.takes_s3(symbols.shape[1], symbols.shape[2]):      # bf16x3: y_hat leaves the dequantisation pre-split
-                y_hat = ops.dequant_split3(symbols, hyper)
-            else:
-                y_hat = ops.dequant_scale_normal(symbols, hyper)
+                y_hat = ops.dequant_split3(symbols, self._hyper_synthesis(z_hat))
+            else:     # mu only: the last hyper-synthesis layer skips its raw-sigma columns where its plan can (same bits)
+                y_hat = ops.dequant_scale_normal(symbols, self._hyper_synthesis.leading_channels(z_hat, symbols.shape[-1]))
             out = self._pixels(y_hat, image_hw, reference)
             if check:
                 ops.check_conv_status()
@@ -577,7 +576,7 @@ class Model:
             for st, (z_hat, sym, _hw, _r) in zip(self._set_streams, codes):
                 st.wait_stream(cur)
                 with torch.cuda.stream(st):
-                    y_hat = ops.dequant_scale_normal(sym, self._hyper_synthesis(z_hat))
+                    y_hat = ops.dequant_scale_normal(sym, self._hyper_synthesis.leading_channels(z_hat, sym.shape[-1]))
                 y_hat.record_stream(cur)
                 y_hats.append(y_hat)
             for st in self._set_streams[:len(codes)]:

@@ -21,6 +21,8 @@ KINDS = {"conv": capi.CONV2D, "convT": capi.CONV2D_TRANSPOSE, "sigdown": capi.SI
 
 WGRAD_STREAM = None         # training: the side stream the weight / bias gradients of TConv layers are launched on (Trainer sets it)
 FUSE_RESIDUAL_TAIL = True   # ResidualBlock (c = 192): 3x3 and 1x1 + skip in one launch (bit-identical; False: two launches)
+MEAN_ONLY_HYPER = True      # decode: the hyper-synthesis' last layer computes its mu channels only (ConvPlan.columns; the same bits as the
+                            # first half of the whole layer; False: the whole layer, for the A/B and the bit-identity tests)
 FUSE_RESIDUAL_BLOCK = not os.environ.get("SNTC_NO_RB_FUSE")   # ResidualBlock (c = 192): head, 3x3 and tail + skip in ONE launch on an 8 x 32
                             # pixel tile with its halo patch in LDS (csrc/rb_fused.hip; bit-identical to the three launches)
 FUSED_BLOCK_MIN_TILES = 256  # ... where the launch offers at least one 8 x 32 tile per CU (one workgroup per CU); below, the layers
@@ -369,6 +371,7 @@ class ConvPlan:
         capi.call("sntc_conv_plan_create", C.byref(desc), _ptr(w), _ptr(b), _stream(), C.byref(self._h))
         torch.cuda.current_stream().synchronize()   # packing reads w/b; they may be freed after this
         self._tuned = {}
+        self._views = {}       # ncols -> ConvPlanColumns (columns()): views of this handle, never registered themselves
         import weakref
         _PLAN_REGISTRY.append(weakref.ref(self))
         if FORCE_TILE:
@@ -382,6 +385,27 @@ class ConvPlan:
             except Exception:
                 pass
             self._h = None
+
+    _ncols = 0     # > 0 on a ConvPlanColumns view: every query and launch below is the column-limited one
+
+    def columns_supported(self, ncols):
+        """True if this plan can launch its first ``ncols`` output channels alone (sntc_conv_columns_supported; no launch)."""
+        return bool(capi.load().sntc_conv_columns_supported(self._h, int(ncols)))
+
+    def columns(self, ncols):
+        """A view of this plan that computes only its first ``ncols`` output channels, as a compact [n, ho, wo, ncols] tensor
+        (sntc_conv_forward_columns): the same handle and packed weights, fewer column tiles, the same bits as
+        ``self(x)[..., :ncols]``.  The view behaves like a plan (call, flops, launch_info, candidates, set_choice, tune) and keeps
+        its own measured choices; it is not a plan of its own in ``_PLAN_REGISTRY`` -- ``export_tuning`` lists its choices under
+        this plan's index.  One view per column count."""
+        ncols = int(ncols)
+        v = self._views.get(ncols)
+        if v is None:
+            if not self.columns_supported(ncols):
+                capi.call("sntc_conv_columns_launch_info", self._h, 1, 1, 1, ncols, None, None, None)     # raises with the reason
+                raise capi.SntcError(capi.ERR_UNSUPPORTED, "column-limited launch not supported by this plan")
+            v = self._views[ncols] = ConvPlanColumns(self, ncols)
+        return v
 
     def update(self, weight, bias=None):
         """Re-pack from new device weights (training step); the arrays are read asynchronously on the current stream."""
@@ -442,14 +466,28 @@ class ConvPlan:
     def flops(self, n, h, w):
         """Algorithmic 2 * MAC FLOPs of a call.  A plan whose input channels were zero-padded by its owner (the SGA adjoint of the
         two-layer synthesis pads 24 gradient channels to 32 for the vector loader) counts the REAL channels only."""
+        if self._ncols:
+            return int(capi.load().sntc_conv_columns_flops(self._h, n, h, w, self._ncols))
         f = int(capi.load().sntc_conv_flops(self._h, n, h, w))
         alg = getattr(self, "algorithmic_cin", None)
         return f if alg is None else f * int(alg) // self.cin
 
     def launch_info(self, n, h, w):
         v, nb = C.c_int(), C.c_int()
-        capi.call("sntc_conv_launch_info", self._h, n, h, w, C.byref(v), C.byref(nb))
+        if self._ncols:
+            capi.call("sntc_conv_columns_launch_info", self._h, n, h, w, self._ncols, C.byref(v), C.byref(nb), None)
+        else:
+            capi.call("sntc_conv_launch_info", self._h, n, h, w, C.byref(v), C.byref(nb))
         return v.value, nb.value
+
+    def launch_order(self, n, h, w):
+        """True if the launch walks its stream-K units column tile outermost (sntc_conv_launch_order; profiling)."""
+        colm = C.c_int()
+        if self._ncols:
+            capi.call("sntc_conv_columns_launch_info", self._h, n, h, w, self._ncols, None, None, C.byref(colm))
+        else:
+            capi.call("sntc_conv_launch_order", self._h, n, h, w, C.byref(colm))
+        return bool(colm.value)
 
     def tune(self, x, res=None, aux=None, reps=3):
         """Time this plan's (tile, schedule) candidates on ``x`` and keep the fastest for calls of this shape
@@ -457,29 +495,49 @@ class ConvPlan:
         n, h, w = (int(v) for v in x.shape[:3])
         ho, wo = self.out_hw(h, w)
         y = torch.empty((n, ho, wo, self.cout), dtype=torch.float32, device=x.device)
-        ws_bytes = int(capi.load().sntc_conv_tune_workspace_bytes(self._h, n, h, w))
-        ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=x.device) if ws_bytes else None
         v, sk = C.c_int(), C.c_int()
-        capi.call("sntc_conv_plan_tune", self._h, _ptr(x), n, h, w, _ptr(y), _ptr(res), _ptr(aux), _ptr(ws), ws_bytes, int(reps),
-                  C.byref(v), C.byref(sk), _stream())
+        if self._ncols:
+            ws_bytes = int(capi.load().sntc_conv_columns_tune_workspace_bytes(self._h, n, h, w, self._ncols))
+            ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=x.device) if ws_bytes else None
+            capi.call("sntc_conv_columns_tune", self._h, _ptr(x), n, h, w, self._ncols, _ptr(y), _ptr(ws), ws_bytes, int(reps),
+                      C.byref(v), C.byref(sk), _stream())
+        else:
+            ws_bytes = int(capi.load().sntc_conv_tune_workspace_bytes(self._h, n, h, w))
+            ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=x.device) if ws_bytes else None
+            capi.call("sntc_conv_plan_tune", self._h, _ptr(x), n, h, w, _ptr(y), _ptr(res), _ptr(aux), _ptr(ws), ws_bytes, int(reps),
+                      C.byref(v), C.byref(sk), _stream())
         self._tuned[(n, h, w)] = (v.value, sk.value)
         return v.value, sk.value
 
     def clear_tuning(self):
+        """Forget every measured choice of this plan, those of its column views included (they live in the same handle)."""
         capi.call("sntc_conv_plan_clear_tuning", self._h)
         self._tuned = {}
+        for v in self._views.values():
+            v._tuned = {}
+
+    def drop_choice(self, n, h, w):
+        """Forget the measured choice of ONE call shape (back to the cost model); every other choice stays."""
+        capi.call("sntc_conv_plan_drop_choice", self._h, int(n), int(h), int(w), self._ncols)
+        self._tuned.pop((int(n), int(h), int(w)), None)
 
     def candidates(self, n, h, w):
         """[(variant, stream_k)] this plan could run a call of this shape with (all give identical bits)."""
         v, s = (C.c_int * 32)(), (C.c_int * 32)()
-        k = int(capi.load().sntc_conv_plan_candidates(self._h, int(n), int(h), int(w), v, s, 32))
+        if self._ncols:
+            k = int(capi.load().sntc_conv_columns_candidates(self._h, int(n), int(h), int(w), self._ncols, v, s, 32))
+        else:
+            k = int(capi.load().sntc_conv_plan_candidates(self._h, int(n), int(h), int(w), v, s, 32))
         if k < 0:
             raise capi.SntcError(capi.ERR_BAD_SHAPE, capi.last_error())
         return [(v[i], s[i]) for i in range(k)]
 
     def set_choice(self, n, h, w, variant, stream_k):
         """Record (variant, stream_k) as the schedule of calls of this shape (sntc_conv_plan_set_choice)."""
-        capi.call("sntc_conv_plan_set_choice", self._h, int(n), int(h), int(w), int(variant), int(bool(stream_k)))
+        if self._ncols:
+            capi.call("sntc_conv_columns_set_choice", self._h, int(n), int(h), int(w), self._ncols, int(variant), int(bool(stream_k)))
+        else:
+            capi.call("sntc_conv_plan_set_choice", self._h, int(n), int(h), int(w), int(variant), int(bool(stream_k)))
         self._tuned[(int(n), int(h), int(w))] = (int(variant), int(bool(stream_k)))
 
     def __call__(self, x, res=None, aux=None, out=None):
@@ -511,17 +569,58 @@ class ConvPlan:
         if prof is not None:     # bench.py: HIP events on the launch stream around this kernel
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        ws_bytes = int(capi.load().sntc_conv_workspace_bytes(self._h, n, h, w))
-        ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=x.device) if ws_bytes else None
-        capi.call("sntc_conv_forward", self._h, _ptr(x), n, h, w, _ptr(y), _ptr(res), _ptr(aux), _ptr(ws), ws_bytes, _stream())
+        if self._ncols:      # the workspace is asked for the column count that is launched: the stream-K partition depends on it
+            ws_bytes = int(capi.load().sntc_conv_columns_workspace_bytes(self._h, n, h, w, self._ncols))
+            ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=x.device) if ws_bytes else None
+            capi.call("sntc_conv_forward_columns", self._h, _ptr(x), n, h, w, _ptr(y), _ptr(res), _ptr(aux), _ptr(ws), ws_bytes, _stream(),
+                      self._ncols)
+        else:
+            ws_bytes = int(capi.load().sntc_conv_workspace_bytes(self._h, n, h, w))
+            ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=x.device) if ws_bytes else None
+            capi.call("sntc_conv_forward", self._h, _ptr(x), n, h, w, _ptr(y), _ptr(res), _ptr(aux), _ptr(ws), ws_bytes, _stream())
         if prof is not None:
             e1.record()
             v, nb = self.launch_info(n, h, w)
-            colm = C.c_int()
-            capi.call("sntc_conv_launch_order", self._h, n, h, w, C.byref(colm))
-            prof.append(dict(e0=e0, e1=e1, flops=self.flops(n, h, w), variant=v, nblocks=nb, vec=self.cin % 16 == 0 or self.rowpack,
-                             kind=self.kind, k=self.k[0], s=self.stride, cin=self.cin, cout=self.cout, n=n, h=h, w=w, colm=bool(colm.value)))
+            # `flops` is the ALGORITHMIC count of the layer as the reference defines it (tests/test_hip_fullsize.py checks the sums
+            # against the reference's FLOPs-per-pixel tables) -- for a column view that is the parent's whole layer, as for a
+            # channel-padded adjoint it is the unpadded one; what this launch multiplies is `launched_flops`
+            prof.append(dict(e0=e0, e1=e1, flops=(self.parent if self._ncols else self).flops(n, h, w), launched_flops=self.flops(n, h, w),
+                             variant=v, nblocks=nb, vec=self.cin % 16 == 0 or self.rowpack,
+                             kind=self.kind, k=self.k[0], s=self.stride, cin=self.cin, cout=self.cout, n=n, h=h, w=w,
+                             colm=self.launch_order(n, h, w)))
         return y
+
+
+class ConvPlanColumns(ConvPlan):
+    """``parent.columns(ncols)``: the parent's first ``ncols`` output channels as a plan-like view over the SAME C handle
+    (sntc_conv_forward_columns).  ``cout`` is ``ncols``; measured choices are the view's own (the handle keys them by column
+    count).  Weights, tile and schedule switches are the parent's."""
+
+    def __init__(self, parent, ncols):
+        self.parent, self._ncols = parent, int(ncols)
+        self.kind, self.cin, self.cout, self.stride, self.k = parent.kind, parent.cin, int(ncols), parent.stride, parent.k
+        self.epilogue, self.bf16x3, self.s3, self.rowpack = parent.epilogue, parent.bf16x3, parent.s3, parent.rowpack
+        self._h = parent._h          # shared: the parent owns and destroys it (and outlives the view: the view holds the parent)
+        self._tuned = {}
+        self._views = {}
+
+    def __del__(self):
+        pass
+
+    def columns(self, ncols):
+        return self.parent.columns(ncols)
+
+    def update(self, weight, bias=None):
+        self.parent.update(weight, bias)
+
+    def clear_tuning(self):
+        self.parent.clear_tuning()
+
+    def fusable_with(self, second):
+        return False
+
+    def fused(self, second, x, res=None, aux=None):
+        raise capi.SntcError(capi.ERR_UNSUPPORTED, "a column-limited view cannot be the first half of a fused pair")
 
 
 def take_conv_status():
@@ -623,10 +722,7 @@ def tune_step(step_fn, reps=12, min_gain=0.004, max_launches=16, log=None, burst
                 if had is not None:
                     plan.set_choice(n, h, w, *had)
                 else:
-                    plan._tuned.pop((n, h, w), None)
-                    capi.call("sntc_conv_plan_clear_tuning", plan._h)    # back to the cost model for every shape of this plan ...
-                    for (nn, hh, ww), (vv, ss) in list(plan._tuned.items()):
-                        capi.call("sntc_conv_plan_set_choice", plan._h, nn, hh, ww, vv, ss)      # ... but the ones already chosen
+                    plan.drop_choice(n, h, w)        # back to the cost model for this shape; the plan's other choices stay
 
             if walk == 0:
                 rollback.append(restore)
@@ -687,6 +783,9 @@ def export_tuning():
             continue
         for (n, h, w), (v, sk) in sorted(p._tuned.items()):
             out.append((idx, p.kind, p.cin, p.cout, int(n), int(h), int(w), int(v), int(sk)))
+        for ncols, view in sorted(p._views.items()):          # a column view's choices: the parent's index, cout = the column count
+            for (n, h, w), (v, sk) in sorted(view._tuned.items()):
+                out.append((idx, p.kind, p.cin, int(ncols), int(n), int(h), int(w), int(v), int(sk)))
     return out
 
 
@@ -705,6 +804,8 @@ def import_tuning(entries, strict=True):
         p = _PLAN_REGISTRY[idx]()
         if p is None:
             continue        # collected here already (the cyclic collector runs at different times on different ranks): nothing to tune
+        if (p.kind, p.cin) == (kind, cin) and 0 < cout < p.cout and p.columns_supported(cout):
+            p = p.columns(cout)         # the choice of a column-limited launch of that plan (export_tuning: cout = its column count)
         if (p.kind, p.cin, p.cout) != (kind, cin, cout):
             if not strict:
                 continue
@@ -1138,12 +1239,20 @@ def entropy_scale_normal(y, hyper, want_symbols=False, values_only=False):
 
 
 def dequant_scale_normal(symbols, hyper):
+    """y_hat = symbols + mu.  ``hyper``: the hyper-synthesis' [mu | raw sigma] output (2 c channels) or its compact mu alone
+    (c channels: the decoder's mean-only hyper-synthesis)."""
     c = symbols.shape[-1]
-    _check_nhwc(hyper, 2 * c)
+    compact = hyper.shape[-1] == c
+    _check_nhwc(hyper, c if compact else 2 * c)
+    if tuple(hyper.shape[:3]) != tuple(symbols.shape[:3]):
+        raise ValueError(f"hyper-synthesis output {tuple(hyper.shape)} does not match symbols {tuple(symbols.shape)}")
     n = symbols.shape[0]
     hw = symbols.shape[1] * symbols.shape[2]
     y_hat = torch.empty(symbols.shape, dtype=torch.float32, device=symbols.device)
-    capi.call("sntc_dequant_scale_normal", _ptr(symbols), _ptr(hyper), n, hw, c, _ptr(y_hat), _stream())
+    if compact:
+        capi.call("sntc_dequant_mean", _ptr(symbols), _ptr(hyper), n, hw, c, c, _ptr(y_hat), _stream())
+    else:
+        capi.call("sntc_dequant_scale_normal", _ptr(symbols), _ptr(hyper), n, hw, c, _ptr(y_hat), _stream())
     return y_hat
 
 
