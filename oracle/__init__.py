@@ -39,6 +39,8 @@ Modules
   train_ref      float64 PyTorch-autograd restatement of the training loss (Model.train_step's forward,
                  mshyper/models.py:234-359,375-383, 'unoise' / 'mixedq') as a transforms_np backend: the
                  gradient reference of tests/test_hip_train.py, plus the Keras-Adam / clipnorm arithmetic.
+  rate_plane     the plane of scale index x deviation (out to |v| = 5000) on which tests/test_hip_rate_plane.py reads the
+                 rate kernels symbol by symbol, its float64 references and the float32 floor of the reference formulation.
   rans_np        pure-Python restatement of THIS build's rANS wire format and table construction (the
                  reference has no bitstream): pins csrc/rans.hip word for word.
   make_golden    generates tests/golden/*.npz from ops_np/transforms_np/rans_np.

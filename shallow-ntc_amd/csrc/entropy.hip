@@ -42,6 +42,9 @@ __device__ __forceinline__ float normal_bits(float v, float sigma) {
 // per symbol, the same instruction stream on every lane (selects, no divergent branches); the far tails need no separate series --
 // erfcx is smooth to infinity.  Against float64 (2e6 synthetic latents, emulated in numpy before it was written): sum of bits
 // within 2e-8 relative, the same as the formulation above (whose bias was the rounding of 1 / ln 2: carried here in two terms).
+// That is a figure of the SUM.  One symbol (the same emulation on the plane of tests/test_hip_rate_plane.py: 102 scales x the
+// integers -70 .. 70 and out to +-5000): min(abs, rel) error up to 1.0e-5 -- at sigma = 256, where cl and e agree to three digits
+// (v = -10: 9.32694 for 9.32684 bits) -- against 6.0e-6 for the reference formulation at float32; the test holds both to 2.4e-5.
 __device__ __forceinline__ float exp_f(float x) {          // exp(x), ~1.5 ulp; underflows to 0, overflows to inf
   const float hi = x * 1.44269502162933349609375f;
   const float lo = fmaf(x, 1.44269502162933349609375f, -hi) + x * 1.925963033500011e-8f;   // log2 e = hi part + 1.926e-8

@@ -45,9 +45,43 @@ __device__ __forceinline__ bool scale_index_gate(float e, float dbits_dsigma) {
   return e <= 63.0f || dbits_dsigma > 0.0f;
 }
 
-// ---- normal (y) : forward sample + rate + partial derivatives ----
+// phi(x) / Phi(x), given lp = log_ndtr_f(x).  Below log_ndtr_f's asymptotic switch ln phi - ln Phi is ln(-x) - ln(series) term
+// by term, so the ratio is -x / series with no exponent at all; above it x^2 / 2 <= 50 and the difference of the two logarithms
+// rounds at 3e-6.  (Subtracting log P from -x^2 / 2 instead, two float32 numbers of size (v / sigma)^2 / 2, loses the ratio
+// from |v| / sigma ~ 180 on.)  One instruction stream: a select, the unselected side may be inf or NaN.
+__device__ __forceinline__ float phi_over_ndtr_f(float x, float lp) {
+  const float ix2 = 1.0f / (x * x);
+  const float series = 1.0f - ix2 * (1.0f - 3.0f * ix2 * (1.0f - 5.0f * ix2));
+  const float near = expf(-0.5f * x * x - 0.91893853320467274f - lp);
+  return x > -10.0f ? near : -x / series;
+}
+
+// ---- normal (y) : rate + partial derivatives at a given sample, for the SGA and the training-mode entry points ----
 // bits(v, sigma) = -log2 [Phi((v+.5)/s) - Phi((v-.5)/s)];  d bits/d v, d bits/d raw (through
 // idx = clamp(exp(raw), 0, 63), sigma = exp(c0 + c1 idx)).
+// With (a, b) the arguments of the (big, small) log_ndtr pair, P = Phi(a) (1 - rho), rho = Phi(b) / Phi(a), and phi is even:
+//   phi(a) / P = [phi / Phi](a) / (1 - rho),   phi(b) / P = [phi / Phi](b) rho / (1 - rho)
+// -- nothing of size (v / sigma)^2 is subtracted on the way to the derivatives.
+__device__ __forceinline__ void normal_rate_terms(float v, float raw, float* bits, float* dbits_dv, float* dbits_draw) {
+  const float e = expf(raw);
+  const float idx = fminf(fmaxf(e, 0.0f), 63.0f);
+  const float sigma = expf(kLogScaleMin + kScaleFactor * idx);
+  const float hi = (v + 0.5f) / sigma, lo = (v - 0.5f) / sigma;
+  const bool right = hi > 0.0f;
+  const float a = right ? -lo : hi, b = right ? -hi : lo;
+  const float big = log_ndtr_f(a), small = log_ndtr_f(b);
+  const float rho = expf(small - big);
+  const float logp = big + log1pf(-rho);
+  const float inv = 1.0f / (1.0f - rho);
+  const float r_big = phi_over_ndtr_f(a, big) * inv, r_small = phi_over_ndtr_f(b, small) * rho * inv;
+  const float r_hi = right ? r_small : r_big, r_lo = right ? r_big : r_small;
+  const float dsig_draw = scale_index_gate(e, (r_hi * hi - r_lo * lo) / sigma) ? sigma * kScaleFactor * e : 0.0f;
+  *bits = -logp * kInvLn2;
+  *dbits_dv = -(r_hi - r_lo) / sigma * kInvLn2;
+  *dbits_draw = (r_hi * hi - r_lo * lo) / sigma * dsig_draw * kInvLn2;
+}
+
+// forward sample + the rate terms at it
 __global__ void __launch_bounds__(256) sga_normal_fwd_kernel(const float* __restrict__ y_loc, const float* __restrict__ hyper,
                                                              int64_t hw, int c, float tau, const float* __restrict__ noise,
                                                              unsigned long long seed, unsigned long long step,
@@ -65,27 +99,14 @@ __global__ void __launch_bounds__(256) sga_normal_fwd_kernel(const float* __rest
     const float raw = hyper[(img * hw + p) * 2 * c + c + ch];
     const float g0 = noise ? noise[2 * gi] : gumbel_from(seed, step, (unsigned long long)gi, 0);
     const float g1 = noise ? noise[2 * gi + 1] : gumbel_from(seed, step, (unsigned long long)gi, 1);
-    float v, sp;
+    float v, sp, b, dv, dr;
     sga_sample(y_loc[gi] - mu, tau, g0, g1, &v, &sp);
-    const float e = expf(raw);
-    const float idx = fminf(fmaxf(e, 0.0f), 63.0f);
-    const float sigma = expf(kLogScaleMin + kScaleFactor * idx);
-    const float hi = (v + 0.5f) / sigma, lo = (v - 0.5f) / sigma;
-    const bool right = hi > 0.0f;
-    const float big = log_ndtr_f(right ? -lo : hi), small = log_ndtr_f(right ? -hi : lo);
-    const float logp = big + log1pf(-expf(small - big));
-    // phi(x)/p in the log domain
-    const float lphi_hi = -0.5f * hi * hi - 0.91893853320467274f - logp;
-    const float lphi_lo = -0.5f * lo * lo - 0.91893853320467274f - logp;
-    const float r_hi = expf(lphi_hi), r_lo = expf(lphi_lo);
-    const float dlogp_dv = (r_hi - r_lo) / sigma;
-    const float dlogp_ds = -(r_hi * hi - r_lo * lo) / sigma;
-    const float dsig_draw = scale_index_gate(e, -dlogp_ds) ? sigma * kScaleFactor * e : 0.0f;
+    normal_rate_terms(v, raw, &b, &dv, &dr);
     y_tilde[gi] = v + mu;
     sprime[gi] = sp;
-    dbits_dv[gi] = -dlogp_dv * kInvLn2;
-    dbits_draw[gi] = -dlogp_ds * dsig_draw * kInvLn2;
-    acc += (double)(-logp * kInvLn2);
+    dbits_dv[gi] = dv;
+    dbits_draw[gi] = dr;
+    acc += (double)b;
   }
   block_sum_to(acc, bits + img);
 }
@@ -380,23 +401,8 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
 
 
 // ---- training-mode entropy terms: the sample is y + U(-.5, .5) (uq method "unoise",
-// mshyper/models.py:253-256,277-280 with training=True); rate and partial derivatives at the given sample ----
-__device__ __forceinline__ void normal_rate_terms(float v, float raw, float* bits, float* dbits_dv, float* dbits_draw) {
-  const float e = expf(raw);
-  const float idx = fminf(fmaxf(e, 0.0f), 63.0f);
-  const float sigma = expf(kLogScaleMin + kScaleFactor * idx);
-  const float hi = (v + 0.5f) / sigma, lo = (v - 0.5f) / sigma;
-  const bool right = hi > 0.0f;
-  const float big = log_ndtr_f(right ? -lo : hi), small = log_ndtr_f(right ? -hi : lo);
-  const float logp = big + log1pf(-expf(small - big));
-  const float r_hi = expf(-0.5f * hi * hi - 0.91893853320467274f - logp);
-  const float r_lo = expf(-0.5f * lo * lo - 0.91893853320467274f - logp);
-  const float dsig_draw = scale_index_gate(e, (r_hi * hi - r_lo * lo) / sigma) ? sigma * kScaleFactor * e : 0.0f;
-  *bits = -logp * kInvLn2;
-  *dbits_dv = -(r_hi - r_lo) / sigma * kInvLn2;
-  *dbits_draw = (r_hi * hi - r_lo * lo) / sigma * dsig_draw * kInvLn2;
-}
-
+// mshyper/models.py:253-256,277-280 with training=True); rate and partial derivatives at the given sample
+// (normal_rate_terms, above) ----
 __global__ void __launch_bounds__(256) noisy_normal_kernel(const float* __restrict__ y_tilde, const float* __restrict__ hyper,
                                                            int64_t hw, int c, float* __restrict__ dbits_dv,
                                                            float* __restrict__ dbits_draw, double* __restrict__ bits) {
