@@ -531,6 +531,39 @@ int sntc_channel_table_ids(int64_t npix, int c, uint16_t* table_ids, void* strea
 int sntc_round_to_int(const float* x, int64_t total, int32_t* out, void* stream);
 int sntc_int_to_float(const int32_t* x, int64_t total, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Quantisation steps off the scale ladder (csrc/quant_step.hip): the reference quantises y - mu with step 1
+ *   and indexes its 64 tables by exp(raw) (mshyper/models.py:273-279); these entry points generalise both lines to a step
+ *   r^k, r = exp((ln 256 - ln 0.11) / 63), k an integer ladder index in [-32, 32]:
+ *     symbol   = (int)rintf((y - mu) * inv_step)   inv_step = float32(r^-k); a float32 subtract, then a float32 multiply
+ *     table id = clamp(base id - k, 0, 63)         base id = sntc_scale_table_ids; the end tables stay off the ladder's ends
+ *     y_hat    = fmaf(step, (float)symbol, mu)     step = float32(r^k)
+ *   sigma_i / r^k = sigma_(i-k): the symbols of step k are distributed as table i - k describes, so the tables, the coder and
+ *   the decoder serve every step.  With step = inv_step = 1.0f, k = 0 these are the symbols of sntc_entropy_scale_normal, the
+ *   ids of sntc_scale_table_ids and the values of sntc_dequant_mean, bit for bit.
+ *   y / symbols / ids: [n][hw][c], c % 4 == 0; mu: `mu_stride` floats per pixel as in sntc_dequant_mean; n <= 65535.
+ * ------------------------------------------------------------------------------------------------------- */
+/* One step per image: inv_step float [n], shift (= k) int32 [n], both on the device.  Writes symbols int32 and the shifted
+ * table_ids uint16.  y / mu / symbols 16-byte aligned, the id arrays 8-byte aligned (checked). */
+int sntc_step_symbols(const float* y, const float* mu, int n, int64_t hw, int c, int mu_stride, const uint16_t* base_ids,
+                      const float* inv_step, const int32_t* shift, int32_t* symbols, uint16_t* table_ids, void* stream);
+/* The id rule alone, for a decoder (it has the ids of its hyper-synthesis and no y): table_ids = clamp(base_ids - shift[image], 0, 63),
+ * [n][elems_per_image]. */
+int sntc_step_table_ids(const uint16_t* base_ids, int n, int64_t elems_per_image, const int32_t* shift, uint16_t* table_ids,
+                        void* stream);
+/* sntc_dequant_mean at one step per image: step float [n] on the device. */
+int sntc_dequant_step(const int32_t* symbols, const float* mu, int n, int64_t hw, int c, int mu_stride, const float* step,
+                      float* y_hat, void* stream);
+/* What sntc_rans_cost would return for the symbols and ids of sntc_step_symbols at each of `nsteps` candidate steps shared by
+ *   the batch (1 <= nsteps <= 16; inv_step float [nsteps], shift int32 [nsteps], on the device), in ONE pass over y, mu and the
+ *   base ids (10 bytes per element), without writing a symbol: cost uint64 [n][nsteps], zeroed by the call, in units of
+ *   2^-16 bit.  meta / cost_q / ntables / total_entries: as sntc_rans_cost; the set holds the ladder's 64 tables first
+ *   (ntables >= 64).  All sums are integers: the result is exact whatever the launch geometry.  Pointers that are not aligned
+ *   for 16-byte loads (y, mu) / 8-byte loads (base_ids) take an element-wise path with the same result. */
+int sntc_step_ladder_cost(const float* y, const float* mu, int n, int64_t hw, int c, int mu_stride, const uint16_t* base_ids,
+                          const float* inv_step, const int32_t* shift, int nsteps, const uint32_t* meta, int ntables,
+                          int total_entries, const uint32_t* cost_q, uint64_t* cost, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * SSIM / MS-SSIM statistics (eval-only quality metrics, reference mshyper/models.py:321-336 ->
  *   tf.image.ssim / tf.image.ssim_multiscale).  Images are float NHWC holding pixel

@@ -16,6 +16,10 @@ Wire format v3 (little endian): b"SNTC" u16 version (low byte 3; high byte = ari
   + the interleaved 16-bit words (csrc/rans.hip).
 The decoder rebuilds mu / scale indexes with the same hyper-synthesis kernels (deterministic, batch-invariant), so
 encoder and decoder agree bit for bit.
+Wire format v5 = v3 with version byte 5 and, between the header and the length fields, n signed bytes: per image the index k of its
+  quantisation step on the scale ladder (``step_size``; STEP_MIN <= k <= STEP_MAX).  y - mu is quantised with the step r^k,
+  r = exp(SCALE_FACTOR), and coded with the table k places down the ladder (sigma_i / r^k = sigma_(i-k): the same 64 tables serve every
+  step; csrc/quant_step.hip).  Written only when some index is non-zero: all zero is the v3 blob, byte for byte.
 
 The factorized-prior model (factorized/models.py) has ONE latent and no hyper-synthesis: ``FactorizedCodec``, wire format v4
   b"SNTC" u16 version (low byte 4; high byte = the arithmetic tag, as above) | u16 n | u32 H | u32 W | u16 C | u16 h | u16 w |
@@ -46,6 +50,67 @@ VERSION_FACTORIZED = 4                    # FactorizedCodec: one latent, table =
 ARITH = {"fp32": 0, "bf16x3": 1}          # Model(precision=...): high byte of the version word
 SCALE_MIN, SCALE_MAX, NUM_SCALES = 0.11, 256.0, 64
 SCALE_FACTOR = (math.log(SCALE_MAX) - math.log(SCALE_MIN)) / (NUM_SCALES - 1.0)
+VERSION_STEP = 5                          # v3 + one signed byte per image: its quantisation step's index on the scale ladder
+STEP_MIN, STEP_MAX = -32, 32              # ladder indexes a file may carry (checked here; the kernels' id clamp absorbs any shift)
+LADDER_MAX = 16                           # candidate steps of one sntc_step_ladder_cost launch
+
+
+def step_size(k):
+    """The quantisation step of ladder index k, exp(k SCALE_FACTOR) = (sigma_(i+k) / sigma_i of the scale ladder), computed in
+    float64 and rounded ONCE to float32 -- the value the kernels multiply with (returned as a Python float holding it).
+    ``step_size(-k)`` is the inverse step the encoder multiplies with.  step_size(0) == 1.0."""
+    k = int(k)
+    if not STEP_MIN <= k <= STEP_MAX:
+        raise ValueError(f"ladder index {k} outside [{STEP_MIN}, {STEP_MAX}]")
+    return float(np.float32(math.exp(k * SCALE_FACTOR)))
+
+
+def check_steps(step, n):
+    """``step`` (an int, or a sequence of n ints) -> list of n ladder indexes; ValueError on anything else."""
+    if isinstance(step, (int, np.integer)) and not isinstance(step, bool):
+        ks = [int(step)] * n
+    else:
+        try:
+            ks = list(step)
+        except TypeError:
+            raise ValueError(f"step must be an int or a sequence of {n} ints, not {step!r}") from None
+        if len(ks) != n:
+            raise ValueError(f"{len(ks)} steps for {n} images")
+        if not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) for k in ks):
+            raise ValueError(f"steps must be ints (indexes on the scale ladder), not {ks!r}")
+        ks = [int(k) for k in ks]
+    for k in ks:
+        if not STEP_MIN <= k <= STEP_MAX:
+            raise ValueError(f"ladder index {k} outside [{STEP_MIN}, {STEP_MAX}]")
+    return ks
+
+
+def check_budgets(target_bpp, n):
+    """``target_bpp`` (a number, or a sequence of n numbers) -> float64 [n]; ValueError on anything else."""
+    t = np.asarray(target_bpp, np.float64)
+    if t.ndim == 0:
+        t = np.full(n, float(t))
+    if t.shape != (n,) or not np.isfinite(t).all():
+        raise ValueError(f"target_bpp must be a finite number or {n} of them, not {target_bpp!r}")
+    return t
+
+
+def select_steps(bits, budget_bits, steps):
+    """The rate-control rule, a pure function: ``bits`` [n, len(steps)] = what image i would pay at ladder index steps[j],
+    ``budget_bits`` [n].  Per image the SMALLEST index (the finest step) whose bits fit the budget -- not the first fit found
+    walking down from a coarse step: a row need not be monotone -- and STEP_MAX, met = False, where none fits.
+    -> list of dict(step_chosen, bits_predicted, budget_bits, met)."""
+    bits = np.asarray(bits, np.float64)
+    steps = [int(k) for k in steps]
+    if bits.ndim != 2 or bits.shape[1] != len(steps) or len(budget_bits) != bits.shape[0]:
+        raise ValueError("select_steps: bits [n, len(steps)] and n budgets")
+    out = []
+    for row, budget in zip(bits, budget_bits):
+        fits = [k for k, b in zip(steps, row) if b <= budget]
+        k = min(fits) if fits else STEP_MAX
+        pred = float(row[steps.index(k)]) if k in steps else float("nan")
+        out.append(dict(step_chosen=k, bits_predicted=pred, budget_bits=float(budget), met=bool(fits)))
+    return out
 
 
 def quantize_pmf(pmf, escape_mass):
@@ -374,6 +439,54 @@ def scale_table_ids(hyper):
     return tid
 
 
+def step_tensors(steps, device):
+    """Ladder indexes -> what the step kernels read, on ``device``: (step float32, inv_step float32, shift int32), one entry
+    per index (``step_size``: float64, rounded once)."""
+    ks = [int(k) for k in steps]
+    host = np.empty((3, len(ks)), np.float32)                      # ONE upload; the third row holds the int32 shifts' bits
+    host[0] = [step_size(k) for k in ks]
+    host[1] = [step_size(-k) for k in ks]
+    host[2].view(np.int32)[:] = ks
+    t = torch.from_numpy(host).to(device)
+    return t[0], t[1], t[2].view(torch.int32)
+
+
+def step_table_ids(base_ids, shift):
+    """``scale_table_ids`` shifted down the ladder: clamp(id - shift[image], 0, 63) (int16 storage of uint16, shape kept);
+    ``shift`` int32 [n] on the device.  What the decoder of a v5 blob indexes its tables with."""
+    n = base_ids.shape[0]
+    if base_ids.dtype != torch.int16 or not base_ids.is_contiguous() or shift.dtype != torch.int32 or shift.numel() != n:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_table_ids: contiguous int16 (uint16 storage) ids and one int32 shift per image")
+    out = torch.empty_like(base_ids)
+    capi.call("sntc_step_table_ids", _p(base_ids), n, base_ids.numel() // n, _p(shift), _p(out), ops._stream())
+    return out
+
+
+def step_ladder_cost(y, hyper, base_ids, steps, tables: DeviceTables, tensors=None):
+    """``rans_cost`` of the symbols and ids ``ops.step_symbols`` would form at EVERY ladder index of ``steps`` (shared by the
+    batch), without forming them: one pass over y / mu / ids per launch of at most ``LADDER_MAX`` candidates.
+    -> int64 [n, len(steps)] on the device, 2^-16 bit.  ``tensors``: ``step_tensors(steps, device)`` if the caller keeps them."""
+    c = y.shape[-1]
+    if y.dtype != torch.float32 or hyper.dtype != torch.float32 or base_ids.dtype != torch.int16 or y.dim() != 4 or hyper.dim() != 4 \
+            or tuple(hyper.shape[:3]) != tuple(y.shape[:3]) or hyper.shape[-1] not in (c, 2 * c) or tuple(base_ids.shape) != tuple(y.shape) \
+            or not (y.is_contiguous() and hyper.is_contiguous() and base_ids.is_contiguous()):
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_ladder_cost: y float32 [n, h, w, c], hyper [n, h, w, c or 2 c], ids int16 like y, contiguous")
+    steps = check_steps(list(steps), len(steps))
+    if not steps:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_ladder_cost: no candidate step")
+    n, hw = y.shape[0], y.shape[1] * y.shape[2]
+    _, inv, sh = step_tensors(steps, y.device) if tensors is None else tensors
+    cost = torch.empty((n, len(steps)), dtype=torch.int64, device=y.device)
+    for lo in range(0, len(steps), LADDER_MAX):
+        k = min(LADDER_MAX, len(steps) - lo)
+        part = cost if k == len(steps) else torch.empty((n, k), dtype=torch.int64, device=y.device)
+        capi.call("sntc_step_ladder_cost", _p(y), _p(hyper), n, hw, c, hyper.shape[-1], _p(base_ids), _p(inv[lo:lo + k]), _p(sh[lo:lo + k]),
+                  k, _p(tables.meta), tables.ntables, tables.total, _p(tables.cost_q), _p(part), ops._stream())
+        if part is not cost:
+            cost[:, lo:lo + k] = part
+    return cost
+
+
 def channel_table_ids(shape, device):
     n, h, w, c = shape
     tid = torch.empty((n, h, w, c), dtype=torch.int16, device=device)
@@ -393,10 +506,76 @@ def int_to_float(x):
     return out
 
 
+# -- wire formats v3 / v5: pure host functions (numbers in, numbers out; no device) ----------------------------------------
+HEAD_V3 = "<HHIIHHHHHHHHBB"               # version | n | H | W | C | Cz | hz | wz | h | w | segments_z | segments_y | lanes_z | lanes_y
+
+
+def pack_v3(arith, n, H, W, dims, sz, sy, lz, ly, zl, yl, steps=None) -> bytes:
+    """Everything of a hyperprior blob in front of the payload.  ``dims`` = (C, Cz, hz, wz, h, w); ``steps``: one ladder index
+    per image, or None.  With every index 0 (or None) this is the v3 header; else version 5: the same header with version
+    byte 5, then the n indexes as signed bytes, then the length fields."""
+    c, cz, hz, wz, h, w = dims
+    steps = [0] * n if steps is None else check_steps(list(steps), n)
+    stepped = any(steps)
+    head = MAGIC + struct.pack(HEAD_V3, (VERSION_STEP if stepped else VERSION) | (arith << 8), n, H, W, c, cz, hz, wz, h, w, sz, sy, lz, ly)
+    if stepped:
+        head += np.asarray(steps, np.int8).tobytes()
+    return head + np.asarray(zl, np.int64).astype("<u4").tobytes() + np.asarray(yl, np.int64).astype("<u4").tobytes()
+
+
+def parse_v3(blob: bytes, precision, latent_shapes):
+    """Header and stream lengths of one v3 / v5 blob, checked against the decoding model: ``precision`` its arithmetic,
+    ``latent_shapes(H, W) -> (C, Cz, hz, wz, h, w)`` its latents for an H x W image.  -> dict(..., steps = the n ladder indexes of
+    a v5 blob or None, pos = payload offset)."""
+    if blob[:4] != MAGIC:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "not an SNTC bitstream")
+    pos = 4 + struct.calcsize(HEAD_V3)
+    if len(blob) < pos:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+    ver, n, H, W, c, cz, hz, wz, h, w, sz, sy, lz, ly = struct.unpack_from(HEAD_V3, blob, 4)
+    arith, ver = ver >> 8, ver & 0xff
+    if ver not in (VERSION, VERSION_STEP):
+        raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream version {ver}")
+    if arith != ARITH[precision]:
+        names = {v: k for k, v in ARITH.items()}
+        raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream was written by a {names.get(arith, arith)!r} model, this model "
+                             f"computes in {precision!r}: mu / sigma would not be reproduced bit for bit")
+    # Every dimension is recomputed from (H, W) and THIS model, so a corrupt or crafted blob cannot size an allocation or
+    # index a table-id tensor beyond what the model itself would produce.
+    if not (1 <= n <= Codec.MAX_IMAGES and 1 <= H <= Codec.MAX_SIDE and 1 <= W <= Codec.MAX_SIDE):
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream header: implausible batch / image size n={n} H={H} W={W}")
+    want = tuple(int(v) for v in latent_shapes(H, W))
+    if (c, cz, hz, wz, h, w) != want:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream header (C, Cz, hz, wz, h, w) = {(c, cz, hz, wz, h, w)} does not match "
+                             f"this model's latents for a {H} x {W} image: {want}")
+    ez, ey = hz * wz * cz, h * w * c
+    if (sz, sy) != (_segments(ez), _segments(ey)) or (lz, ly) != (_lanes(-(-ez // sz)), _lanes(-(-ey // sy))):
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream header: segment / lane counts do not match the latent sizes")
+    steps = None
+    if ver == VERSION_STEP:
+        if len(blob) < pos + n:
+            raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+        steps = np.frombuffer(blob, np.int8, n, pos).astype(np.int64).tolist()
+        pos += n
+        if not all(STEP_MIN <= k <= STEP_MAX for k in steps):
+            raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream header: quantisation step index outside [{STEP_MIN}, {STEP_MAX}]")
+    nz, ny = n * sz, n * sy
+    if len(blob) < pos + 4 * (nz + ny):
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+    zl = np.frombuffer(blob, "<u4", nz, pos).astype(np.int64)
+    yl = np.frombuffer(blob, "<u4", ny, pos + 4 * nz).astype(np.int64)
+    pos += 4 * (nz + ny)
+    zw, yw = int(zl.sum()), int(yl.sum())
+    if len(blob) != pos + 2 * (zw + yw):
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+    return dict(n=n, H=H, W=W, c=c, cz=cz, hz=hz, wz=wz, h=h, w=w, sz=sz, sy=sy, lz=lz, ly=ly, zl=zl, yl=yl, pos=pos, zw=zw, yw=yw,
+                steps=steps)
+
+
 class Codec:
     """compress / decompress for a mean-scale hyperprior ``Model``."""
 
-    HEAD = "<HHIIHHHHHHHHBB"
+    HEAD = HEAD_V3
     MAX_IMAGES, MAX_SIDE = 4096, 1 << 16
 
     def __init__(self, model):
@@ -426,23 +605,47 @@ class Codec:
                                  f"{H} x {W}: {(n, hz, wz, cz)} / {(n, h, w, c)}")
         return n, H, W
 
-    def _symbols(self, z, y):
-        """(z_loc, y_loc) -> what the file carries: (zi int32, z's table ids, y symbols int32, y's table ids, hyper)."""
-        m = self.m
-        zi = round_to_int(z)
-        hyper = m._hyper_synthesis(int_to_float(zi))
-        _, _, sym = ops.entropy_scale_normal(y, hyper, want_symbols=True)
-        return zi, channel_table_ids(z.shape, m.device), sym, scale_table_ids(hyper), hyper
+    def _steps(self, step, n):
+        """``step`` of the public entry points -> None (today's path: step 1 for every image) or the n ladder indexes."""
+        if step is None:
+            return None
+        ks = check_steps(step, n)
+        if self.m._precision != "fp32":
+            raise NotImplementedError(f"quantisation steps run in precision 'fp32', not {self.m._precision!r}: the pre-split "
+                                      "dequantisation is not extended")
+        return ks if any(ks) else None
 
-    def _launch_latents(self, z, y, image_hw):
+    def _step_tensors(self, steps):
+        """``step_tensors`` of ladder indexes on the model's device (one small upload, on the current stream)."""
+        return step_tensors(steps, self.m.device)
+
+    def _hyper_of(self, z):
+        """z_loc -> (zi int32, the hyper-synthesis of it): what every step shares."""
+        zi = round_to_int(z)
+        return zi, self.m._hyper_synthesis(int_to_float(zi))
+
+    def _symbols(self, z, y, steps=None, pre=None):
+        """(z_loc, y_loc) -> what the file carries: (zi int32, z's table ids, y symbols int32, y's table ids, hyper).
+        ``steps``: None, or one ladder index per image (csrc/quant_step.hip); ``pre``: ``_hyper_of(z)`` if the caller has it."""
+        m = self.m
+        zi, hyper = self._hyper_of(z) if pre is None else pre
+        ztid = channel_table_ids(z.shape, m.device)
+        if steps is None:
+            _, _, sym = ops.entropy_scale_normal(y, hyper, want_symbols=True)
+            return zi, ztid, sym, scale_table_ids(hyper), hyper
+        _, inv, sh = self._step_tensors(steps)
+        sym, ytid = ops.step_symbols(y, hyper, scale_table_ids(hyper), inv, sh)
+        return zi, ztid, sym, ytid, hyper
+
+    def _launch_latents(self, z, y, image_hw, steps=None, pre=None):
         """The device half of ``compress_latents`` on the current stream, no host synchronisation."""
         n, H, W = self._check_latents(z, y, image_hw)
-        zi, ztid, sym, ytid, _ = self._symbols(z, y)
+        zi, ztid, sym, ytid, _ = self._symbols(z, y, steps, pre)
         sz, sy = _segments(zi[0].numel()), _segments(sym[0].numel())
         lz, ly = _lanes(-(-zi[0].numel() // sz)), _lanes(-(-sym[0].numel() // sy))
         zs, zlen = rans_encode_launch(zi, ztid, self.z_tables, sz, lz)
         ys, ylen = rans_encode_launch(sym, ytid, self.y_tables, sy, ly)
-        return dict(n=n, H=H, W=W, z=z, y=y, sz=sz, sy=sy, lz=lz, ly=ly, zs=zs, zlen=zlen, ys=ys, ylen=ylen)
+        return dict(n=n, H=H, W=W, z=z, y=y, sz=sz, sy=sy, lz=lz, ly=ly, zs=zs, zlen=zlen, ys=ys, ylen=ylen, steps=steps)
 
     def _finish(self, jobs):
         """Launched jobs -> their blobs: the stream lengths of ALL jobs come back in one copy, the packed payloads in another."""
@@ -460,38 +663,95 @@ class Codec:
         for j in jobs:
             z, y = j["z"], j["y"]
             zw, yw = int(j["zl"].sum()), int(j["yl"].sum())
-            head = MAGIC + struct.pack(self.HEAD, VERSION | (ARITH[m._precision] << 8), j["n"], j["H"], j["W"], y.shape[-1], z.shape[-1],
-                                       z.shape[1], z.shape[2], y.shape[1], y.shape[2], j["sz"], j["sy"], j["lz"], j["ly"])
-            out.append(head + j["zl"].astype("<u4").tobytes() + j["yl"].astype("<u4").tobytes() + words[o:o + zw + yw].tobytes())
+            head = pack_v3(ARITH[m._precision], j["n"], j["H"], j["W"], (y.shape[-1], z.shape[-1], z.shape[1], z.shape[2], y.shape[1], y.shape[2]),
+                           j["sz"], j["sy"], j["lz"], j["ly"], j["zl"], j["yl"], j.get("steps"))
+            out.append(head + words[o:o + zw + yw].tobytes())
             o += zw + yw
         return out
 
-    def compress_latents(self, z_loc, y_loc, image_hw) -> bytes:
+    def compress_latents(self, z_loc, y_loc, image_hw, step=None) -> bytes:
         """Latents of this model for images of ``image_hw`` = (H, W) -- the encoder's, or ones refined by iterative inference --
         -> the bitstream ``decompress`` reads: z is rounded, the hyper-synthesis gives mu / the scale indexes, y - mu is rounded,
-        both are coded.  ``compress(x)`` is this on ``infer_latent_rvs(x)``."""
+        both are coded.  ``compress(x)`` is this on ``infer_latent_rvs(x)``.  ``step``: an index on the scale ladder, or one per
+        image: y - mu is quantised with the step ``step_size(k)`` and coded with the tables k places down the ladder (wire
+        format 5; with every index 0 the v3 blob of ``step=None``, byte for byte)."""
         m = self.m
+        steps = self._steps(step, z_loc.shape[0])
         with torch.cuda.device(m.device):
-            return self._finish([self._launch_latents(z_loc.contiguous(), y_loc.contiguous(), image_hw)])[0]
+            return self._finish([self._launch_latents(z_loc.contiguous(), y_loc.contiguous(), image_hw, steps)])[0]
 
-    def latents_cost(self, z_loc, y_loc, x):
+    def latents_cost(self, z_loc, y_loc, x, step=None):
         """What ``compress_latents`` would write for these latents and what ``decompress`` would make of it, without writing it:
         -> (cost_z, cost_y int64 [n] in 2^-16 bit (``rans_cost``), uint8 pixels, integer SSE [n] against ``x``), all on the
-        device, no host synchronisation."""
+        device, no host synchronisation.  ``step`` as in ``compress_latents``."""
         m = self.m
         n, H, W = self._check_latents(z_loc, y_loc, x.shape[1:3])
-        zi, ztid, sym, ytid, hyper = self._symbols(z_loc.contiguous(), y_loc.contiguous())
+        steps = self._steps(step, n)
+        zi, ztid, sym, ytid, hyper = self._symbols(z_loc.contiguous(), y_loc.contiguous(), steps)
         cost_z, cost_y = rans_cost(zi, ztid, self.z_tables), rans_cost(sym, ytid, self.y_tables)
-        y_hat = ops.dequant_split3(sym, hyper) if m._synthesis.takes_s3(sym.shape[1], sym.shape[2]) else ops.dequant_scale_normal(sym, hyper)
+        if steps is not None:
+            y_hat = ops.dequant_step(sym, hyper, self._step_tensors(steps)[0])
+        else:
+            y_hat = ops.dequant_split3(sym, hyper) if m._synthesis.takes_s3(sym.shape[1], sym.shape[2]) else ops.dequant_scale_normal(sym, hyper)
         px, sse = m._pixels(y_hat, (H, W), x)                     # the decoder's own steps from the symbols on
         return cost_z, cost_y, px, sse
 
-    def compress(self, x) -> bytes:
+    def _ladder(self, z, y, steps, pre=None):
+        zi, hyper = self._hyper_of(z) if pre is None else pre
+        cost_z = rans_cost(zi, channel_table_ids(z.shape, self.m.device), self.z_tables)
+        cost_y = step_ladder_cost(y, hyper, scale_table_ids(hyper), steps, self.y_tables, self._step_tensors(steps))
+        return cost_z, cost_y
+
+    def ladder_cost(self, z_loc, y_loc, image_hw, steps):
+        """``latents_cost``'s (cost_z, cost_y) at EVERY ladder index of ``steps`` without forming a symbol tensor: -> (cost_z
+        int64 [n], cost_y int64 [n, len(steps)]) in 2^-16 bit on the device, no host synchronisation.  y, mu and the scale
+        indexes are read once per launch of at most ``LADDER_MAX`` candidates (csrc/quant_step.hip)."""
+        steps = check_steps(list(steps), len(steps))
+        if not steps:
+            raise ValueError("ladder_cost: no candidate step")
+        if self.m._precision != "fp32":
+            raise NotImplementedError(f"quantisation steps run in precision 'fp32', not {self.m._precision!r}")
+        self._check_latents(z_loc, y_loc, image_hw)
+        with torch.cuda.device(self.m.device):
+            return self._ladder(z_loc.contiguous(), y_loc.contiguous(), steps)
+
+    def flushed_bits(self, H, W):
+        """The lane states every image's streams flush, in bits: 32 per lane and stream (in the file, not in ``rans_cost``)."""
+        c, cz, hz, wz, h, w = self.latent_shapes(H, W)
+        ez, ey = hz * wz * cz, h * w * c
+        sz, sy = _segments(ez), _segments(ey)
+        return 32 * (sz * _lanes(-(-ez // sz)) + sy * _lanes(-(-ey // sy)))
+
+    def compress(self, x, step=None, target_bpp=None) -> bytes:
+        """``step``: as in ``compress_latents``.  ``target_bpp`` (a number, or one per image): rate control -- per image the
+        finest step of the whole ladder whose predicted bits (``ladder_cost`` + the flushed lane states; header and length
+        fields not counted) are within target_bpp H W, STEP_MAX where none is.  One encoder pass, the ladder launches, one
+        read-back, the coding launches.  ``last_report``: per image step_chosen, bits_predicted, budget_bits, met."""
         m = self.m
         x = m._as_device_images(x)
+        n, H, W = x.shape[0], int(x.shape[1]), int(x.shape[2])
+        if step is not None and target_bpp is not None:
+            raise ValueError("compress: step and target_bpp exclude each other")
+        steps = self._steps(step, n)
+        budgets = None
+        if target_bpp is not None:
+            budgets = check_budgets(target_bpp, n) * float(H * W)
+            if m._precision != "fp32":
+                raise NotImplementedError(f"quantisation steps run in precision 'fp32', not {m._precision!r}")
         with torch.cuda.device(m.device):
             lat = m.infer_latent_rvs(x)
-            return self.compress_latents(lat.uq[0].loc, lat.uq[1].loc, x.shape[1:3])
+            z, y = lat.uq[0].loc.contiguous(), lat.uq[1].loc.contiguous()
+            if budgets is None:
+                return self._finish([self._launch_latents(z, y, (H, W), steps)])[0]
+            self._check_latents(z, y, (H, W))
+            ladder = list(range(STEP_MIN, STEP_MAX + 1))
+            pre = self._hyper_of(z)
+            cost_z, cost_y = self._ladder(z, y, ladder, pre)
+            host = torch.cat([cost_z[:, None], cost_y], dim=1).cpu().numpy()                                     # the one read-back
+            bits = (host[:, :1] + host[:, 1:]) / float(COST_UNIT) + float(self.flushed_bits(H, W))
+            self.last_report = select_steps(bits, budgets, ladder)
+            chosen = [r["step_chosen"] for r in self.last_report]
+            return self._finish([self._launch_latents(z, y, (H, W), chosen if any(chosen) else None, pre)])[0]
 
     def compress_many(self, xs):
         """``compress`` for several batches (e.g. one per image size of a set) -> their bitstreams, in order, byte for byte what one
@@ -521,41 +781,10 @@ class Codec:
 
     def _parse(self, blob: bytes):
         """Header and stream lengths of one blob, checked against THIS model: nothing later trusts the header."""
-        m = self.m
-        if blob[:4] != MAGIC:
-            raise capi.SntcError(capi.ERR_BAD_SHAPE, "not an SNTC bitstream")
-        pos = 4 + struct.calcsize(self.HEAD)
-        if len(blob) < pos:
-            raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
-        ver, n, H, W, c, cz, hz, wz, h, w, sz, sy, lz, ly = struct.unpack_from(self.HEAD, blob, 4)
-        arith, ver = ver >> 8, ver & 0xff
-        if ver != VERSION:
-            raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream version {ver}")
-        if arith != ARITH[m._precision]:
-            names = {v: k for k, v in ARITH.items()}
-            raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream was written by a {names.get(arith, arith)!r} model, this model "
-                                 f"computes in {m._precision!r}: mu / sigma would not be reproduced bit for bit")
-        # Every dimension is recomputed from (H, W) and THIS model, so a corrupt or crafted blob cannot size an allocation or
-        # index a table-id tensor beyond what the model itself would produce.
-        if not (1 <= n <= self.MAX_IMAGES and 1 <= H <= self.MAX_SIDE and 1 <= W <= self.MAX_SIDE):
-            raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream header: implausible batch / image size n={n} H={H} W={W}")
-        want = self.latent_shapes(H, W)
-        if (c, cz, hz, wz, h, w) != want:
-            raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream header (C, Cz, hz, wz, h, w) = {(c, cz, hz, wz, h, w)} does not match "
-                                 f"this model's latents for a {H} x {W} image: {want}")
-        ez, ey = hz * wz * cz, h * w * c
-        if (sz, sy) != (_segments(ez), _segments(ey)) or (lz, ly) != (_lanes(-(-ez // sz)), _lanes(-(-ey // sy))):
-            raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream header: segment / lane counts do not match the latent sizes")
-        nz, ny = n * sz, n * sy
-        if len(blob) < pos + 4 * (nz + ny):
-            raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
-        zl = np.frombuffer(blob, "<u4", nz, pos).astype(np.int64)
-        yl = np.frombuffer(blob, "<u4", ny, pos + 4 * nz).astype(np.int64)
-        pos += 4 * (nz + ny)
-        zw, yw = int(zl.sum()), int(yl.sum())
-        if len(blob) != pos + 2 * (zw + yw):
-            raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
-        return dict(n=n, H=H, W=W, c=c, cz=cz, hz=hz, wz=wz, h=h, w=w, sz=sz, sy=sy, lz=lz, ly=ly, zl=zl, yl=yl, pos=pos, zw=zw, yw=yw)
+        hd = parse_v3(blob, self.m._precision, self.latent_shapes)
+        if hd["steps"] is not None and self.m._precision != "fp32":
+            raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream version {VERSION_STEP} (quantisation steps) decodes in precision 'fp32' only")
+        return hd
 
     def decompress(self, blob: bytes):
         return self.decompress_many([blob])[0]
@@ -590,6 +819,8 @@ class Codec:
             host[8 * noff:].view(np.int16)[:] = np.concatenate(words)
             up = torch.from_numpy(host).to(dev)
             off_d, word_d = up[:8 * noff].view(torch.int64), up[8 * noff:].view(torch.int16)
+            # v5: every blob's step tensors go up here too, before anything is enqueued; they are read on the caller's stream only
+            stepd = [None if hd["steps"] is None else self._step_tensors(hd["steps"]) for hd in heads]
             pay, offd = [], []
             o = wpos = 0
             for hd in heads:
@@ -644,6 +875,8 @@ class Codec:
                                          f"{(hd['n'], hd['h'], hd['w'], hd['c'])}")
                 hypers[k] = hyper
                 tidl[k] = scale_table_ids(hyper)
+                if hd["steps"] is not None:      # v5: the tables k places down the ladder, the decoder's start tables unchanged
+                    tidl[k] = step_table_ids(tidl[k], stepd[k][2])
                 if piped:
                     launch_latents(k)
             if not piped:                    # A/B (PIPELINE_BLOBS = False), round 4's schedule: every hyper-synthesis, then every blob's
@@ -660,7 +893,10 @@ class Codec:
                     main.wait_stream(st)
                     syms[k].record_stream(main)
                 with ops.static_schedules(piped and i + 1 < len(order)):
-                    y_hat = ops.dequant_split3(syms[k], hypers[k]) if m._synthesis.takes_s3(hd["h"], hd["w"]) else ops.dequant_scale_normal(syms[k], hypers[k])
+                    if hd["steps"] is not None:
+                        y_hat = ops.dequant_step(syms[k], hypers[k], stepd[k][0])
+                    else:
+                        y_hat = ops.dequant_split3(syms[k], hypers[k]) if m._synthesis.takes_s3(hd["h"], hd["w"]) else ops.dequant_scale_normal(syms[k], hypers[k])
                     out[k] = m._pixels(y_hat, (hd["H"], hd["W"]))
             nbad = int(bad.sum().item())                           # synchronises the stream
             if nbad:

@@ -76,7 +76,8 @@ class Model(_ms.Model):
                 ops.check_conv_status()
         return y_hat, None, None, bits
 
-    def decode(self, y_hat, symbols, image_hw, reference=None, check=True):
+    def decode(self, y_hat, symbols, image_hw, reference=None, check=True, step=None):
+        self._check_step_arguments("decode", step)          # NotImplementedError: quantisation steps are the hyperprior models'
         with torch.cuda.device(self.device):
             recon = self._synthesis(y_hat)
             if reference is None:

@@ -546,11 +546,18 @@ class Model:
                 ops.check_conv_status()
         return z_hat, sym, bits_z, bits_y
 
-    def decode(self, z_hat, symbols, image_hw, reference=None, check=True):
+    def decode(self, z_hat, symbols, image_hw, reference=None, check=True, step=None):
         """(z_hat, symbols) -> hyper-synthesis -> y_hat = symbols + mu -> synthesis -> uint8 pixels
-        [n, H, W, 3] (and the per-image integer SSE against ``reference`` if given).  ``check`` as in ``encode``."""
+        [n, H, W, 3] (and the per-image integer SSE against ``reference`` if given).  ``check`` as in ``encode``.
+        ``step``: the ladder index (or one per image) the symbols were quantised with (``compress(step=...)``):
+        y_hat = fma(step_size(k), symbols, mu)."""
+        self._check_step_arguments("decode", step)
+        steps = None if step is None else self._get_codec()._steps(step, symbols.shape[0])
         with torch.cuda.device(self.device):
-            if self._synthesis.takes_s3(symbols.shape[1], symbols.shape[2]):      # bf16x3: y_hat leaves the dequantisation pre-split
+            if steps is not None:
+                mu = self._hyper_synthesis.leading_channels(z_hat, symbols.shape[-1])
+                y_hat = ops.dequant_step(symbols, mu, self._get_codec()._step_tensors(steps)[0])
+            elif self._synthesis.takes_s3(symbols.shape[1], symbols.shape[2]):      # bf16x3: y_hat leaves the dequantisation pre-split
                 y_hat = ops.dequant_split3(symbols, self._hyper_synthesis(z_hat))
             else:     # mu only: the last hyper-synthesis layer skips its raw-sigma columns where its plan can (same bits)
                 y_hat = ops.dequant_scale_normal(symbols, self._hyper_synthesis.leading_channels(z_hat, symbols.shape[-1]))
@@ -622,7 +629,7 @@ class Model:
             self._codec = Codec(self)
         return self._codec
 
-    def compress(self, x, itinf=None) -> bytes:
+    def compress(self, x, itinf=None, step=None, target_bpp=None) -> bytes:
         """Images -> self-contained bitstream (rANS over the integer CDF tables of both entropy models).
         ``itinf`` = dict(steps, seed=0, check_every=None): refine the latents of THESE images by SGA iterative inference first
         (``initialize_itinf`` + ``steps`` x ``itinf_train_step(x, seed=seed, fetch=False)`` under the model's own tau / learning-rate
@@ -630,28 +637,61 @@ class Model:
         own latents (step 0), every ``check_every``-th step if given, and the last step -- so the file is never worse, by J, than
         that of ``compress(x)``.  ``last_compress_report`` then lists, per image, step_chosen, J_start, J_chosen, bits_start,
         bits_chosen, and ``last_compress_latents`` holds what was coded.  Needs latent_config uq.method == 'sga' and precision
-        'fp32'; leaves the model in iterative-inference mode, as ``initialize_itinf`` does."""
-        if itinf is None:
+        'fp32'; leaves the model in iterative-inference mode, as ``initialize_itinf`` does.
+        ``step`` (an index k on the scale ladder, entropy_coding.STEP_MIN .. STEP_MAX, or one per image): quantise y - mu with
+        the step entropy_coding.step_size(k) = r^k instead of 1 and code with the tables k places down the ladder -- other rates
+        from the same weights; step 0 is the file of ``compress(x)``, byte for byte.
+        ``target_bpp`` (a number, or one per image): per image the finest step whose predicted payload fits target_bpp H W bits,
+        STEP_MAX where none does; ``last_compress_report`` lists step_chosen, bits_predicted, budget_bits, met.
+        An escaped symbol travels in 16 bits: at index k the file clamps |y - mu| beyond 32767 step_size(k) (639 at k = -32),
+        while ``coded_cost`` decodes the unclamped symbol -- the known limit of the format, 1 / step_size(k) closer at fine steps.
+        Mean-scale hyperprior models in precision 'fp32' only; ``step``, ``target_bpp`` and ``itinf`` exclude each other."""
+        self._check_step_arguments("compress", step, target_bpp, itinf)
+        if itinf is not None:
+            return self._compress_itinf(x, **itinf)
+        if step is None and target_bpp is None:
             return self._get_codec().compress(x)
-        return self._compress_itinf(x, **itinf)
+        codec = self._get_codec()
+        blob = codec.compress(x, step=step, target_bpp=target_bpp)
+        if target_bpp is not None:
+            self.last_compress_report = codec.last_report
+        return blob
 
-    def coded_cost(self, x, latent_rvs=None):
-        """Per image, the cost of what ``decompress`` will output for ``latent_rvs`` (None: the encoder's latents of x), without
+    def _check_step_arguments(self, where, step, target_bpp=None, itinf=None):
+        """The refusals of the quantisation-step arguments that need no image: every one before any launch."""
+        if step is None and target_bpp is None:
+            return
+        if self.factorized:
+            raise NotImplementedError(f"{where}(step / target_bpp): a factorized-prior model's per-channel tables would have to be "
+                                      "rebuilt per step; mean-scale hyperprior models only")
+        if step is not None and target_bpp is not None:
+            raise ValueError(f"{where}: step and target_bpp exclude each other")
+        if itinf is not None:
+            raise ValueError(f"{where}: step / target_bpp and itinf exclude each other")
+        if self._precision != "fp32":
+            raise NotImplementedError(f"{where}(step / target_bpp) runs in precision 'fp32', not {self._precision!r}: the pre-split "
+                                      "dequantisation is not extended")
+
+    def coded_cost(self, x, latent_rvs=None, step=None):
+        """Per image, the cost of what ``decompress`` will output for ``latent_rvs`` (None: the encoder's latents of x) coded at
+        ``step`` (None: step 1; a ladder index or one per image as in ``compress``), without
         writing a file: dict of float64 arrays [n] -- ``bits_z`` / ``bits_y`` = ``entropy_coding.rans_cost`` of the symbols the
         file would carry (the coder's 16-bit integer tables, ESCAPE + 16 raw bits; the flushed lane states and the coder's
         rounding slack, DESIGN.md 4.7, are not in it), ``bits`` their sum, ``sse`` the integer SSE of the decoded uint8 pixels,
         ``D`` = the MSE of those pixels on the 0-255 scale (``distortion="ms_ssim"``: 1 - (MS-)SSIM of them, and ``msssim``),
         ``J`` = bits / (H W) + ``lam`` * D with ``lam`` the scheduled rd_lambda.  One host read-back."""
+        self._check_step_arguments("coded_cost", step)
         x = self._as_device_images(x)
         n, h, w, c = x.shape
         ssim = self._distortion == "ms_ssim"
         if ssim:
             ops.msssim_scale_sizes(h, w)                              # ValueError before any launch
         codec = self._get_codec()
+        kw = {} if step is None else dict(step=codec._steps(step, n))
         with torch.cuda.device(self.device):
             if latent_rvs is None:
                 latent_rvs = self.infer_latent_rvs(x)
-            cost_z, cost_y, px, sse = codec.latents_cost(*[rv.loc for rv in latent_rvs.uq], x)
+            cost_z, cost_y, px, sse = codec.latents_cost(*[rv.loc for rv in latent_rvs.uq], x, **kw)
             rows = [torch.zeros_like(cost_y) if cost_z is None else cost_z, cost_y, sse]
             parts = [torch.stack(rows).to(torch.float64).flatten()]   # integers below 2^53: exact
             if ssim:

@@ -1256,6 +1256,47 @@ def dequant_scale_normal(symbols, hyper):
     return y_hat
 
 
+def _check_step_inputs(a, hyper, per_image):
+    """Shared checks of the quantisation-step kernels (csrc/quant_step.hip): ``hyper`` = [mu | raw sigma] (2 c channels) or a
+    compact mu (c channels); ``per_image`` float32 / int32 tensors with one entry per image.  -> (n, hw, c, mu_stride)."""
+    if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dim() == 4 and a.is_contiguous()):
+        raise ValueError(f"expected a contiguous NHWC CUDA tensor, got {type(a).__name__} {tuple(getattr(a, 'shape', ()))}")
+    c = a.shape[-1]
+    compact = hyper.shape[-1] == c
+    _check_nhwc(hyper, c if compact else 2 * c)
+    if tuple(hyper.shape[:3]) != tuple(a.shape[:3]):
+        raise ValueError(f"hyper-synthesis output {tuple(hyper.shape)} does not match latents {tuple(a.shape)}")
+    n = a.shape[0]
+    for t in per_image:
+        if t.numel() != n or not t.is_contiguous() or t.device != a.device:
+            raise ValueError(f"one step per image: {t.numel()} entries for {n} images")
+    return n, a.shape[1] * a.shape[2], c, hyper.shape[-1]
+
+
+def step_symbols(y, hyper, base_ids, inv_step, shift):
+    """Quantisation at one ladder step per image (entropy_coding.step_tensors: ``inv_step`` float32 [n], ``shift`` int32 [n]):
+    -> (symbols int32 = rint((y - mu) * inv_step), table ids = clamp(base_ids - shift, 0, 63) as int16 storage)."""
+    n, hw, c, stride = _check_step_inputs(y, hyper, (inv_step, shift))
+    if base_ids.dtype != torch.int16 or tuple(base_ids.shape) != tuple(y.shape) or not base_ids.is_contiguous() \
+            or inv_step.dtype != torch.float32 or shift.dtype != torch.int32:
+        raise ValueError("step_symbols: base_ids int16 (uint16 storage) like y, inv_step float32, shift int32")
+    sym = torch.empty(y.shape, dtype=torch.int32, device=y.device)
+    tid = torch.empty_like(base_ids)
+    capi.call("sntc_step_symbols", _ptr(y), _ptr(hyper), n, hw, c, stride, _ptr(base_ids), _ptr(inv_step), _ptr(shift), _ptr(sym),
+              _ptr(tid), _stream())
+    return sym, tid
+
+
+def dequant_step(symbols, hyper, step):
+    """y_hat = fma(step[image], symbols, mu): ``dequant_scale_normal`` at one ladder step per image (``step`` float32 [n])."""
+    n, hw, c, stride = _check_step_inputs(symbols, hyper, (step,))
+    if symbols.dtype != torch.int32 or step.dtype != torch.float32:
+        raise ValueError("dequant_step: symbols int32, step float32")
+    y_hat = torch.empty(symbols.shape, dtype=torch.float32, device=symbols.device)
+    capi.call("sntc_dequant_step", _ptr(symbols), _ptr(hyper), n, hw, c, stride, _ptr(step), _ptr(y_hat), _stream())
+    return y_hat
+
+
 # ------------------------------------------------------------------------------------------
 # SGA iterative inference (include/sntc.h "SGA" section)
 # ------------------------------------------------------------------------------------------
