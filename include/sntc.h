@@ -633,6 +633,27 @@ int sntc_sga_normal_fwd(const float* y_loc, const float* hyper, int n, int64_t h
 /* g_yloc = (g_ytilde + weight dbits_dv) sprime;  g_hyper = [g_ytilde (1 - sprime) - weight dbits_dv sprime | weight dbits_draw] */
 int sntc_sga_normal_bwd(const float* g_ytilde, const float* sprime, const float* dbits_dv, const float* dbits_draw,
                         float weight, int64_t npix, int c, float* g_yloc, float* g_hyper, void* stream);
+/* sntc_sga_normal_fwd at one quantisation step per image (mshyper/models.py:285-291 and common/latent_rvs_utils.py:8-48 on the
+ * grid of the step; the step rule is that of sntc_step_symbols / sntc_dequant_step above): quant_step float [n] = r^k,
+ * inv_step float [n] = r^-k, shift int32 [n] = k, on the device.  Per element, in float32:
+ *   u = (y_loc - mu) * inv_step;  (v, sprime) = sga_round(u, tau) and d v / d u;  y~ = fmaf(quant_step, v, mu);
+ *   sigma = exp(c0 + c1 clamp(clamp(exp(raw), 0, 63) - k, 0, 63));  bits[n] = -sum log2 p_N(v; sigma);
+ *   dbits_dv = d bits / d v;  dbits_draw = d bits / d raw (identity-if-towards on the inner clamp, the plain clamp gradient
+ *   on the outer one: zero where the shifted index leaves [0, 63]).
+ * Where u is an integer y~ is sntc_dequant_step's value of sntc_step_symbols' symbol.  The Gumbel draw has the keys of
+ * sntc_sga_normal_fwd; with quant_step = inv_step = 1.0f, k = 0 the four element-wise outputs are that entry point's, bit for
+ * bit.  c % 4 == 0 and 16-byte aligned pointers take 16-byte loads and stores, anything else an element-wise path with the
+ * same result.  n <= 65535. */
+int sntc_sga_normal_step_fwd(const float* y_loc, const float* hyper, int n, int64_t hw, int c, float tau, const float* noise,
+                             uint64_t seed, uint64_t step, const float* quant_step, const float* inv_step, const int32_t* shift,
+                             float* y_tilde, float* sprime, float* dbits_dv, float* dbits_draw, double* bits, void* stream);
+/* Its backward half (mshyper/models.py:285-291, common/latent_rvs_utils.py:8-48): with a = sprime inv_step, dv = weight dbits_dv,
+ * g = g_ytilde dweight[image] (dweight float [n] on the device: the image's weight on the distortion gradient),
+ *   g_yloc = (g quant_step + dv) a;  g_hyper = [g (1 - quant_step a) - dv a | weight dbits_draw]
+ * -- sntc_sga_normal_bwd's operations at quant_step = inv_step = dweight = 1.0f. */
+int sntc_sga_normal_step_bwd(const float* g_ytilde, const float* sprime, const float* dbits_dv, const float* dbits_draw,
+                             float weight, int n, int64_t hw, int c, const float* quant_step, const float* inv_step,
+                             const float* dweight, float* g_yloc, float* g_hyper, void* stream);
 /* UQLatentRV.sample(training, method, offset, **kwargs) / .quantize(offset) (common/latent_rvs_lib.py:77-116) on [npix, c]
  * values: u = loc - offset (offset NULL = none; else element (p, ch) is offset[p * offset_stride + ch], e.g. the mean half of
  * the hyper-synthesis output with offset_stride = 2 c; offset_stride 0 broadcasts a per-channel [c] offset).  mode 0: round-half-even(u) + offset (training=False, :95-102; also

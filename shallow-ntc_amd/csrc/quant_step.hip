@@ -6,6 +6,7 @@
 //   symbol    s = (int)rintf((y - mu) * inv_step)            float32 subtract, then float32 multiply
 //   table id  t = clamp(t0 - k, 0, 63)                       t0 = sntc_scale_table_ids; off the ladder's ends the end table stays
 //   value     y_hat = fmaf(step, (float)s, mu)
+// The symbol and value rules live in step_rules.h: SGA at a step (sga.hip) samples and dequantises with the same functions.
 // At k = 0 (step = inv_step = 1.0f) they are the symbols of sntc_entropy_scale_normal, the ids of sntc_scale_table_ids and the
 // values of sntc_dequant_mean, bit for bit.
 //
@@ -17,6 +18,7 @@
 // chain id -> descriptor -> symbol -> price across both pipes; no counter run has split the two.
 #include <algorithm>
 #include "rans_common.h"
+#include "step_rules.h"
 
 namespace sntc {
 
@@ -26,17 +28,11 @@ constexpr int kLadderThreads = 1024;
 constexpr int kLadderGrid = 512;                            // workgroups of a launch, about
 constexpr int kLadderLdsLimit = kRansLdsTotal;              // descriptors + cost_q staged in LDS up to here
 
-__device__ __forceinline__ float step_diff(float y, float mu) { return y - mu; }
-
-__device__ __forceinline__ int step_round(float d, float inv_step) { return (int)rintf(d * inv_step); }
-
 __device__ __forceinline__ int step_symbol(float y, float mu, float inv_step) { return step_round(step_diff(y, mu), inv_step); }
 
 __device__ __forceinline__ unsigned step_table_id(unsigned t0, int shift) {
   return (unsigned)min(max((int)t0 - shift, 0), kLadderTop);
 }
-
-__device__ __forceinline__ float step_value(int s, float mu, float step) { return fmaf(step, (float)s, mu); }
 
 typedef int qs_i32x4 __attribute__((ext_vector_type(4)));
 typedef float qs_f32x4 __attribute__((ext_vector_type(4)));

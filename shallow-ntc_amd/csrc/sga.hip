@@ -10,6 +10,7 @@
 #include <cmath>
 #include <algorithm>
 #include "device_math.h"
+#include "step_rules.h"
 
 namespace sntc {
 
@@ -29,7 +30,9 @@ __device__ __forceinline__ void sga_sample(float mu, float tau, float g0, float 
   const float l0 = -atanhf(a) / tau, l1 = -atanhf(b) / tau;
   const float d = ((l1 + g1) - (l0 + g0)) / tau;
   const float w1 = 1.0f / (1.0f + expf(-d));
-  *out = (1.0f - w1) * fl + w1 * ce;
+  // At an integer mu floor == ceil and the sample IS mu; the float32 combination of two equal ends can miss it by an ulp
+  // ((1 - w) 3 + w 3 != 3 for one w in sixteen), and SGA at a quantisation step promises the coder's own value there.
+  *out = fl == ce ? mu : (1.0f - w1) * fl + w1 * ce;
   // d l0 / d mu = -1/(tau (1-a^2)) unless clipped; d l1 / d mu = +1/(tau (1-b^2)) unless clipped
   const bool a_free = (mu - fl) < 1.0f - kSgaEps, b_free = (ce - mu) < 1.0f - kSgaEps;
   const float dl0 = a_free ? -1.0f / (tau * (1.0f - a * a)) : 0.0f;
@@ -62,10 +65,15 @@ __device__ __forceinline__ float phi_over_ndtr_f(float x, float lp) {
 // With (a, b) the arguments of the (big, small) log_ndtr pair, P = Phi(a) (1 - rho), rho = Phi(b) / Phi(a), and phi is even:
 //   phi(a) / P = [phi / Phi](a) / (1 - rho),   phi(b) / P = [phi / Phi](b) rho / (1 - rho)
 // -- nothing of size (v / sigma)^2 is subtracted on the way to the derivatives.
-__device__ __forceinline__ void normal_rate_terms(float v, float raw, float* bits, float* dbits_dv, float* dbits_draw) {
+// At a quantisation step r^k v counts steps and the scale is the one k places down the ladder, as the coder's
+// table id is (quant_step.hip step_table_id): j = idx - k, idx' = clamp(j, 0, 63), sigma = exp(c0 + c1 idx').  The outer clamp is
+// this project's own and takes the plain clamp gradient (it passes iff 0 <= j <= 63); the gate above stays on the inner one.
+// shift = 0: j = idx, both additions to the rule vanish -- the sample-space entry points below pass 0.
+__device__ __forceinline__ void normal_rate_terms_at(float v, float raw, float shift, float* bits, float* dbits_dv, float* dbits_draw) {
   const float e = expf(raw);
   const float idx = fminf(fmaxf(e, 0.0f), 63.0f);
-  const float sigma = expf(kLogScaleMin + kScaleFactor * idx);
+  const float j = idx - shift;
+  const float sigma = expf(kLogScaleMin + kScaleFactor * fminf(fmaxf(j, 0.0f), 63.0f));
   const float hi = (v + 0.5f) / sigma, lo = (v - 0.5f) / sigma;
   const bool right = hi > 0.0f;
   const float a = right ? -lo : hi, b = right ? -hi : lo;
@@ -75,10 +83,15 @@ __device__ __forceinline__ void normal_rate_terms(float v, float raw, float* bit
   const float inv = 1.0f / (1.0f - rho);
   const float r_big = phi_over_ndtr_f(a, big) * inv, r_small = phi_over_ndtr_f(b, small) * rho * inv;
   const float r_hi = right ? r_small : r_big, r_lo = right ? r_big : r_small;
-  const float dsig_draw = scale_index_gate(e, (r_hi * hi - r_lo * lo) / sigma) ? sigma * kScaleFactor * e : 0.0f;
+  const bool open = scale_index_gate(e, (r_hi * hi - r_lo * lo) / sigma) && j >= 0.0f && j <= 63.0f;
+  const float dsig_draw = open ? sigma * kScaleFactor * e : 0.0f;
   *bits = -logp * kInvLn2;
   *dbits_dv = -(r_hi - r_lo) / sigma * kInvLn2;
   *dbits_draw = (r_hi * hi - r_lo * lo) / sigma * dsig_draw * kInvLn2;
+}
+
+__device__ __forceinline__ void normal_rate_terms(float v, float raw, float* bits, float* dbits_dv, float* dbits_draw) {
+  normal_rate_terms_at(v, raw, 0.0f, bits, dbits_dv, dbits_draw);
 }
 
 // forward sample + the rate terms at it
@@ -124,6 +137,124 @@ __global__ void __launch_bounds__(256) sga_normal_bwd_kernel(const float* __rest
     g_yloc[i] = (g + dv) * sp;
     g_hyper[p * 2 * c + ch] = g * (1.0f - sp) - dv * sp;
     g_hyper[p * 2 * c + c + ch] = w * dbits_draw[i];
+  }
+}
+
+// ---- the same two kernels at one quantisation step per image (reference mshyper/models.py:285-291 with
+// common/latent_rvs_utils.py:8-48 on the step's grid) ----
+// u = (y_loc - mu) inv_step, (v, s') = sga_sample(u), y~ = fma(step, v, mu): where u is an integer, y~ is what sntc_dequant_step
+// returns for the coder's symbol.  The rate is normal_rate_terms_at(v, raw, k).  The Gumbel draw has the keys of
+// sga_normal_fwd_kernel: (seed, step, element index in the batch).
+// Layout of step_symbols_kernel (quant_step.hip): grid (blocks per image, n); a thread's unit is V consecutive channels of a
+// pixel (V = 4: 16-byte loads and stores, c % 4 == 0 and aligned pointers; V = 1 otherwise).
+template <int V>
+__global__ void __launch_bounds__(256) sga_normal_step_fwd_kernel(const float* __restrict__ y_loc, const float* __restrict__ hyper,
+                                                                  long long hw, int c, float tau, const float* __restrict__ noise,
+                                                                  unsigned long long seed, unsigned long long step,
+                                                                  const float* __restrict__ qstep, const float* __restrict__ inv_step,
+                                                                  const int* __restrict__ shift, float* __restrict__ y_tilde,
+                                                                  float* __restrict__ sprime, float* __restrict__ dbits_dv,
+                                                                  float* __restrict__ dbits_draw, double* __restrict__ bits) {
+  const int img = blockIdx.y, cu = c / V;                    // units per pixel
+  const float st = qstep[img], inv = inv_step[img], k = (float)shift[img];
+  const long long nunit = hw * cu, base = (long long)img * hw * c;
+  double acc = 0.0;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nunit; i += (long long)gridDim.x * blockDim.x) {
+    const long long p = i / cu;
+    const int ch = (int)(i - p * cu) * V;
+    const long long gi = base + i * V;                       // first element of the unit, index in the batch
+    const float* hp = hyper + ((long long)img * hw + p) * 2 * c + ch;
+    float y[V], mu[V], raw[V], g[2 * V], yt[V], sp[V], dv[V], dr[V];
+    if constexpr (V == 4) {
+      const f32x4 yv = *reinterpret_cast<const f32x4*>(y_loc + gi);
+      const f32x4 mv = *reinterpret_cast<const f32x4*>(hp);
+      const f32x4 rv = *reinterpret_cast<const f32x4*>(hp + c);
+#pragma unroll
+      for (int e = 0; e < V; ++e) { y[e] = yv[e]; mu[e] = mv[e]; raw[e] = rv[e]; }
+      if (noise) {
+        const f32x4 n0 = *reinterpret_cast<const f32x4*>(noise + 2 * gi);
+        const f32x4 n1 = *reinterpret_cast<const f32x4*>(noise + 2 * gi + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { g[e] = n0[e]; g[4 + e] = n1[e]; }
+      }
+    } else {
+      y[0] = y_loc[gi];
+      mu[0] = hp[0];
+      raw[0] = hp[c];
+      if (noise) { g[0] = noise[2 * gi]; g[1] = noise[2 * gi + 1]; }
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const float g0 = noise ? g[2 * e] : gumbel_from(seed, step, (unsigned long long)(gi + e), 0);
+      const float g1 = noise ? g[2 * e + 1] : gumbel_from(seed, step, (unsigned long long)(gi + e), 1);
+      float v, b;
+      sga_sample(step_scaled(step_diff(y[e], mu[e]), inv), tau, g0, g1, &v, &sp[e]);
+      normal_rate_terms_at(v, raw[e], k, &b, &dv[e], &dr[e]);
+      yt[e] = step_value_at(v, mu[e], st);
+      acc += (double)b;
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<f32x4*>(y_tilde + gi) = f32x4{yt[0], yt[1], yt[2], yt[3]};
+      *reinterpret_cast<f32x4*>(sprime + gi) = f32x4{sp[0], sp[1], sp[2], sp[3]};
+      *reinterpret_cast<f32x4*>(dbits_dv + gi) = f32x4{dv[0], dv[1], dv[2], dv[3]};
+      *reinterpret_cast<f32x4*>(dbits_draw + gi) = f32x4{dr[0], dr[1], dr[2], dr[3]};
+    } else {
+      y_tilde[gi] = yt[0];
+      sprime[gi] = sp[0];
+      dbits_dv[gi] = dv[0];
+      dbits_draw[gi] = dr[0];
+    }
+  }
+  block_sum_to(acc, bits + img);
+}
+
+// With a = s' inv_step, dv = w dbits_dv, g = g_yt dweight[image] (the image's lambda over the launch's):
+//   g_yloc = (g step + dv) a;   g_mu = g (1 - step a) - dv a;   g_raw = w dbits_draw
+// -- at step = inv_step = dweight = 1 every operation is sga_normal_bwd_kernel's.
+template <int V>
+__global__ void __launch_bounds__(256) sga_normal_step_bwd_kernel(const float* __restrict__ g_yt, const float* __restrict__ sprime,
+                                                                  const float* __restrict__ dbits_dv, const float* __restrict__ dbits_draw,
+                                                                  float w, long long hw, int c, const float* __restrict__ qstep,
+                                                                  const float* __restrict__ inv_step, const float* __restrict__ dweight,
+                                                                  float* __restrict__ g_yloc, float* __restrict__ g_hyper) {
+  const int img = blockIdx.y, cu = c / V;
+  const float st = qstep[img], inv = inv_step[img], dw = dweight[img];
+  const long long nunit = hw * cu, base = (long long)img * hw * c;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nunit; i += (long long)gridDim.x * blockDim.x) {
+    const long long p = i / cu;
+    const int ch = (int)(i - p * cu) * V;
+    const long long gi = base + i * V;
+    float* hp = g_hyper + ((long long)img * hw + p) * 2 * c + ch;
+    float gt[V], sp[V], bv[V], br[V], gy[V], gm[V], gr[V];
+    if constexpr (V == 4) {
+      const f32x4 a0 = *reinterpret_cast<const f32x4*>(g_yt + gi);
+      const f32x4 a1 = *reinterpret_cast<const f32x4*>(sprime + gi);
+      const f32x4 a2 = *reinterpret_cast<const f32x4*>(dbits_dv + gi);
+      const f32x4 a3 = *reinterpret_cast<const f32x4*>(dbits_draw + gi);
+#pragma unroll
+      for (int e = 0; e < V; ++e) { gt[e] = a0[e]; sp[e] = a1[e]; bv[e] = a2[e]; br[e] = a3[e]; }
+    } else {
+      gt[0] = g_yt[gi];
+      sp[0] = sprime[gi];
+      bv[0] = dbits_dv[gi];
+      br[0] = dbits_draw[gi];
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const float g = gt[e] * dw, a = sp[e] * inv, dv = w * bv[e];
+      gy[e] = (g * st + dv) * a;
+      gm[e] = g * (1.0f - st * a) - dv * a;
+      gr[e] = w * br[e];
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<f32x4*>(g_yloc + gi) = f32x4{gy[0], gy[1], gy[2], gy[3]};
+      *reinterpret_cast<f32x4*>(hp) = f32x4{gm[0], gm[1], gm[2], gm[3]};
+      *reinterpret_cast<f32x4*>(hp + c) = f32x4{gr[0], gr[1], gr[2], gr[3]};
+    } else {
+      g_yloc[gi] = gy[0];
+      hp[0] = gm[0];
+      hp[c] = gr[0];
+    }
   }
 }
 
@@ -645,6 +776,60 @@ extern "C" int sntc_sga_normal_bwd(const float* g_ytilde, const float* sprime, c
     return fail(SNTC_ERR_BAD_SHAPE, "sntc_sga_normal_bwd: null argument");
   hipLaunchKernelGGL(sga_normal_bwd_kernel, dim3(grid_for(npix * c)), dim3(256), 0, (hipStream_t)stream, g_ytilde, sprime,
                      dbits_dv, dbits_draw, weight, npix, c, g_yloc, g_hyper);
+  SNTC_HIP(hipGetLastError());
+  return SNTC_OK;
+}
+
+static bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+// Workgroups per image of the step kernels: one unit per thread up to 512 workgroups, beyond that the fewest passes of equal
+// length.  (Four units per thread, step_symbols_kernel's launch, left 2160 workgroups for 18 x 32 x 48 x 320 latents -- 2.1 rounds
+// of the device at this kernel's occupancy, the last one nearly empty: 10 % slower than one element per thread)
+static unsigned step_grid(int64_t nunit) {
+  const int64_t need = (nunit + 255) / 256, passes = (need + 511) / 512;
+  return (unsigned)std::max<int64_t>((need + passes - 1) / passes, 1);
+}
+
+extern "C" int sntc_sga_normal_step_fwd(const float* y_loc, const float* hyper, int n, int64_t hw, int c, float tau,
+                                        const float* noise, uint64_t seed, uint64_t step, const float* quant_step,
+                                        const float* inv_step, const int32_t* shift, float* y_tilde, float* sprime,
+                                        float* dbits_dv, float* dbits_draw, double* bits, void* stream) {
+  if (!y_loc || !hyper || !quant_step || !inv_step || !shift || !y_tilde || !sprime || !dbits_dv || !dbits_draw || !bits)
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_sga_normal_step_fwd: null argument");
+  if (n < 1 || n > 65535 || hw < 1 || c < 1 || !(tau > 0.0f))
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_sga_normal_step_fwd: bad sizes / tau (1 <= n <= 65535)");
+  hipStream_t s = (hipStream_t)stream;
+  if (int zrc = zero_async(bits, sizeof(double) * n, s)) return zrc;
+  const bool vec = c % 4 == 0 && aligned16(y_loc) && aligned16(hyper) && (!noise || aligned16(noise)) && aligned16(y_tilde) &&
+                   aligned16(sprime) && aligned16(dbits_dv) && aligned16(dbits_draw);
+  const int* sh = reinterpret_cast<const int*>(shift);
+  if (vec)
+    hipLaunchKernelGGL((sga_normal_step_fwd_kernel<4>), dim3(step_grid(hw * (c / 4)), n), dim3(256), 0, s, y_loc, hyper, (long long)hw, c,
+                       tau, noise, (unsigned long long)seed, (unsigned long long)step, quant_step, inv_step, sh, y_tilde, sprime,
+                       dbits_dv, dbits_draw, bits);
+  else
+    hipLaunchKernelGGL((sga_normal_step_fwd_kernel<1>), dim3(step_grid(hw * c), n), dim3(256), 0, s, y_loc, hyper, (long long)hw, c,
+                       tau, noise, (unsigned long long)seed, (unsigned long long)step, quant_step, inv_step, sh, y_tilde, sprime,
+                       dbits_dv, dbits_draw, bits);
+  SNTC_HIP(hipGetLastError());
+  return SNTC_OK;
+}
+
+extern "C" int sntc_sga_normal_step_bwd(const float* g_ytilde, const float* sprime, const float* dbits_dv, const float* dbits_draw,
+                                        float weight, int n, int64_t hw, int c, const float* quant_step, const float* inv_step,
+                                        const float* dweight, float* g_yloc, float* g_hyper, void* stream) {
+  if (!g_ytilde || !sprime || !dbits_dv || !dbits_draw || !quant_step || !inv_step || !dweight || !g_yloc || !g_hyper)
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_sga_normal_step_bwd: null argument");
+  if (n < 1 || n > 65535 || hw < 1 || c < 1) return fail(SNTC_ERR_BAD_SHAPE, "sntc_sga_normal_step_bwd: bad sizes (1 <= n <= 65535)");
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = c % 4 == 0 && aligned16(g_ytilde) && aligned16(sprime) && aligned16(dbits_dv) && aligned16(dbits_draw) &&
+                   aligned16(g_yloc) && aligned16(g_hyper);
+  if (vec)
+    hipLaunchKernelGGL((sga_normal_step_bwd_kernel<4>), dim3(step_grid(hw * (c / 4)), n), dim3(256), 0, s, g_ytilde, sprime, dbits_dv,
+                       dbits_draw, weight, (long long)hw, c, quant_step, inv_step, dweight, g_yloc, g_hyper);
+  else
+    hipLaunchKernelGGL((sga_normal_step_bwd_kernel<1>), dim3(step_grid(hw * c), n), dim3(256), 0, s, g_ytilde, sprime, dbits_dv,
+                       dbits_draw, weight, (long long)hw, c, quant_step, inv_step, dweight, g_yloc, g_hyper);
   SNTC_HIP(hipGetLastError());
   return SNTC_OK;
 }

@@ -743,15 +743,20 @@ class Codec:
             z, y = lat.uq[0].loc.contiguous(), lat.uq[1].loc.contiguous()
             if budgets is None:
                 return self._finish([self._launch_latents(z, y, (H, W), steps)])[0]
-            self._check_latents(z, y, (H, W))
-            ladder = list(range(STEP_MIN, STEP_MAX + 1))
-            pre = self._hyper_of(z)
-            cost_z, cost_y = self._ladder(z, y, ladder, pre)
-            host = torch.cat([cost_z[:, None], cost_y], dim=1).cpu().numpy()                                     # the one read-back
-            bits = (host[:, :1] + host[:, 1:]) / float(COST_UNIT) + float(self.flushed_bits(H, W))
-            self.last_report = select_steps(bits, budgets, ladder)
+            self.last_report, pre = self._rate_control(z, y, H, W, budgets)
             chosen = [r["step_chosen"] for r in self.last_report]
             return self._finish([self._launch_latents(z, y, (H, W), chosen if any(chosen) else None, pre)])[0]
+
+    def _rate_control(self, z, y, H, W, budget_bits):
+        """The rate-control pass of ``compress(x, target_bpp=...)`` on given latents: the whole ladder priced in one pass, the
+        flushed lane states counted, ``select_steps``.  -> (the per-image report, ``_hyper_of(z)`` for the coding launches)."""
+        self._check_latents(z, y, (H, W))
+        ladder = list(range(STEP_MIN, STEP_MAX + 1))
+        pre = self._hyper_of(z)
+        cost_z, cost_y = self._ladder(z, y, ladder, pre)
+        host = torch.cat([cost_z[:, None], cost_y], dim=1).cpu().numpy()                                         # the one read-back
+        bits = (host[:, :1] + host[:, 1:]) / float(COST_UNIT) + float(self.flushed_bits(H, W))
+        return select_steps(bits, budget_bits, ladder), pre
 
     def compress_many(self, xs):
         """``compress`` for several batches (e.g. one per image size of a set) -> their bitstreams, in order, byte for byte what one

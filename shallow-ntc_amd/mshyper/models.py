@@ -39,6 +39,39 @@ HIGHER_LAMBDA_UNTIL = 0.2
 HIGHER_LAMBDA_FACTOR = 10.0
 
 
+def step_lambdas(lam, steps, rd_lambda=None):
+    """The weight of each image's distortion at its quantisation step, a pure function: -> float64 [n].  Default
+    lambda_i = lam / step_size(k_i)^2: in the high-resolution regime D grows as the square of the step while the rate falls by
+    log2 of it per element, so the slope -dR/dD the weights were trained to scales with step^-2 (a modelling choice,
+    DESIGN.md 4.7).  ``rd_lambda``: a positive finite number, or one per image, instead."""
+    from ..entropy_coding import step_size
+    n = len(steps)
+    if rd_lambda is None:
+        return np.array([float(lam) / step_size(k) ** 2 for k in steps], np.float64)
+    try:
+        lams = np.asarray(rd_lambda, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"rd_lambda must be a positive finite number or {n} of them, not {rd_lambda!r}") from None
+    if lams.ndim == 0:
+        lams = np.full(n, float(lams))
+    if lams.shape != (n,) or not np.isfinite(lams).all() or not (lams > 0).all():
+        raise ValueError(f"rd_lambda must be a positive finite number or {n} of them, not {rd_lambda!r}")
+    return lams
+
+
+def candidate_wins(j_cand, bits_cand, j_best, bits_best, budget_bits=None, flushed_bits=0.0, met=None):
+    """The selection rule of ``compress(x, itinf=...)``, a pure function over per-image arrays: -> bool [n], True where the
+    candidate replaces the image's best so far.  Without budgets: a strictly smaller J (the earlier candidate wins a tie).
+    With ``budget_bits`` (``target_bpp``): where ``met`` (the start candidate fits) a candidate is eligible only if
+    bits + flushed_bits <= budget, and wins by a strictly smaller J among the eligible; where not, the fewest bits win."""
+    j_cand, bits_cand = np.asarray(j_cand, np.float64), np.asarray(bits_cand, np.float64)
+    j_best, bits_best = np.asarray(j_best, np.float64), np.asarray(bits_best, np.float64)
+    if budget_bits is None:
+        return j_cand < j_best
+    eligible = bits_cand + float(flushed_bits) <= np.asarray(budget_bits, np.float64)
+    return np.where(np.asarray(met, bool), eligible & (j_cand < j_best), bits_cand < bits_best)
+
+
 def deep_factorized_shapes(channels, num_filters=(3, 3)):
     filters = (1,) + tuple(num_filters) + (1,)
     d = OrderedDict()
@@ -386,9 +419,10 @@ class Model:
             return None
         return ops.image_quality(ops.pixels_float(x, h, w), ops.pixels_float(recon, h, w), 255.0)
 
-    def _finish_metrics(self, x_shape, bits_z, bits_y, sse, msssim=None, sched=None):
+    def _finish_metrics(self, x_shape, bits_z, bits_y, sse, msssim=None, sched=None, lams=None):
         """``sched`` = (scheduled_lr, sched_rd_lambda, tau) of the step the numbers belong to, when that is not the current one
-        (metrics of an SGA step fetched later)."""
+        (metrics of an SGA step fetched later).  ``lams``: one lambda per image (SGA at a quantisation step): rd_loss =
+        bpp + mean_i(lambda_i D_i); every other scalar is unchanged."""
         n, h, w, c = x_shape
         num_pixels = np.float32(h * w)                                                  # :302
         bits_z = None if bits_z is None else bits_z.astype(np.float32)
@@ -407,6 +441,9 @@ class Model:
             if msssim is None:
                 raise ValueError("distortion='ms_ssim': no (MS-)SSIM was computed for this frame")
             rd_loss = np.float32(bpp + np.float32(lam) * np.float32(1.0 - np.asarray(msssim, np.float64).mean()))
+        if lams is not None:
+            d = 1.0 - np.asarray(msssim, np.float64) if self._distortion == "ms_ssim" else mses.astype(np.float64)
+            rd_loss = np.float32(bpp + np.float32((np.asarray(lams, np.float64) * d).mean()))
         if not np.isfinite(rd_loss):                                                    # :356
             raise capi.NonFiniteError(capi.ERR_NONFINITE, "rd_loss : Tensor had NaN/Inf values")
         metrics = Metrics.make()
@@ -645,7 +682,18 @@ class Model:
         STEP_MAX where none does; ``last_compress_report`` lists step_chosen, bits_predicted, budget_bits, met.
         An escaped symbol travels in 16 bits: at index k the file clamps |y - mu| beyond 32767 step_size(k) (639 at k = -32),
         while ``coded_cost`` decodes the unclamped symbol -- the known limit of the format, 1 / step_size(k) closer at fine steps.
-        Mean-scale hyperprior models in precision 'fp32' only; ``step``, ``target_bpp`` and ``itinf`` exclude each other."""
+        Mean-scale hyperprior models in precision 'fp32' only; ``step``, ``target_bpp`` and ``itinf`` exclude each other.
+        Refinement AT a step travels inside the dict: ``itinf`` = dict(steps, ..., step=k | [k_i], rd_lambda=None) runs SGA on the
+        grid of step_size(k_i) with the rate of the tables k_i places down the ladder, judges the candidates by
+        ``coded_cost(x, latents, step=ks)`` and writes ``compress_latents(..., step=ks)``; every index 0 is the file of
+        ``itinf=dict(steps, ...)``, byte for byte.  Image i's distortion is weighted with lambda_i = lambda / step_size(k_i)^2
+        (``rd_lambda``: a number or one per image instead) in the loss descended and in J_i = bits_i / (H W) + lambda_i D_i, so
+        "never a worse file, by J" holds at each image's own step and weight.  ``itinf`` = dict(steps, ..., target_bpp=b | [b_i]):
+        the steps are chosen from the ENCODER's latents exactly as ``compress(x, target_bpp=b)`` chooses them, refinement runs at
+        those steps, a candidate is eligible only while its bits + the flushed lane states fit the image's budget (where no step
+        fits, the candidate with the fewest bits wins), and the steps are NOT chosen again after refinement -- a refined image may
+        leave room in its budget that a finer step would have used.  The report then adds quant_step, lam, and with
+        ``target_bpp`` budget_bits, met."""
         self._check_step_arguments("compress", step, target_bpp, itinf)
         if itinf is not None:
             return self._compress_itinf(x, **itinf)
@@ -672,14 +720,15 @@ class Model:
             raise NotImplementedError(f"{where}(step / target_bpp) runs in precision 'fp32', not {self._precision!r}: the pre-split "
                                       "dequantisation is not extended")
 
-    def coded_cost(self, x, latent_rvs=None, step=None):
+    def coded_cost(self, x, latent_rvs=None, step=None, lam=None):
         """Per image, the cost of what ``decompress`` will output for ``latent_rvs`` (None: the encoder's latents of x) coded at
         ``step`` (None: step 1; a ladder index or one per image as in ``compress``), without
         writing a file: dict of float64 arrays [n] -- ``bits_z`` / ``bits_y`` = ``entropy_coding.rans_cost`` of the symbols the
         file would carry (the coder's 16-bit integer tables, ESCAPE + 16 raw bits; the flushed lane states and the coder's
         rounding slack, DESIGN.md 4.7, are not in it), ``bits`` their sum, ``sse`` the integer SSE of the decoded uint8 pixels,
         ``D`` = the MSE of those pixels on the 0-255 scale (``distortion="ms_ssim"``: 1 - (MS-)SSIM of them, and ``msssim``),
-        ``J`` = bits / (H W) + ``lam`` * D with ``lam`` the scheduled rd_lambda.  One host read-back."""
+        ``J`` = bits / (H W) + ``lam`` * D with ``lam`` the scheduled rd_lambda (``lam`` given: one weight per image instead, as
+        ``compress(x, itinf=dict(step=...))`` judges its candidates).  One host read-back."""
         self._check_step_arguments("coded_cost", step)
         x = self._as_device_images(x)
         n, h, w, c = x.shape
@@ -700,6 +749,8 @@ class Model:
             host = torch.cat(parts).cpu().numpy()
             ops.check_conv_status()
         out = dict(bits_z=host[:n] / 65536.0, bits_y=host[n:2 * n] / 65536.0, sse=host[2 * n:3 * n], lam=float(self._scheduled_rd_lambda))
+        if lam is not None:
+            out["lam"] = step_lambdas(1.0, [0] * n, lam)                   # the checks of rd_lambda: positive, finite, one per image
         out["bits"] = out["bits_z"] + out["bits_y"]
         out["D"] = out["sse"] / float(h * w * c)
         if ssim:
@@ -708,7 +759,7 @@ class Model:
         out["J"] = out["bits"] / float(h * w) + out["lam"] * out["D"]
         return out
 
-    def _compress_itinf(self, x, steps, seed=0, check_every=None):
+    def _compress_itinf(self, x, steps, seed=0, check_every=None, step=None, rd_lambda=None, target_bpp=None):
         if self._latent_config["uq"].get("method", "unoise") != "sga":       # every refusal before any launch
             raise NotImplementedError("itinf_train_step implements latent_config uq.method == 'sga'")
         if self._precision != "fp32":
@@ -716,29 +767,67 @@ class Model:
         steps = int(steps)
         if steps < 0 or (check_every is not None and int(check_every) < 1):
             raise ValueError("compress(itinf=...): steps >= 0, check_every None or >= 1")
+        stepped = step is not None or target_bpp is not None or rd_lambda is not None
+        n = 1 if len(tuple(x.shape)) == 3 else int(x.shape[0])
+        budgets = None
+        if stepped:
+            from ..entropy_coding import check_budgets
+            if step is not None and target_bpp is not None:
+                raise ValueError("compress(itinf=...): step and target_bpp exclude each other")
+            quant = self._itinf_quant_of(n, 0 if step is None else step, rd_lambda)
+            if target_bpp is not None:
+                budgets = check_budgets(target_bpp, n)
         x = self._as_device_images(x)
-        n = x.shape[0]
         if self._distortion == "ms_ssim":
             ops.msssim_scale_sizes(x.shape[1], x.shape[2])
         codec = self._get_codec()
-        self.initialize_itinf(x)
+        if not stepped:
+            self.initialize_itinf(x)
+            cost_kw = lat_kw = {}
+            flushed = 0.0
+        else:
+            H, W = int(x.shape[1]), int(x.shape[2])
+            flushed = float(codec.flushed_bits(H, W))
+            self.initialize_itinf(x)
+            control = None
+            if budgets is not None:             # the steps of compress(x, target_bpp=b): chosen from the encoder's latents, once
+                budgets = budgets * float(H * W)
+                with torch.cuda.device(self.device):
+                    control = codec._rate_control(*[rv.loc.contiguous() for rv in self.latent_rvs.uq], H, W, budgets)[0]
+                quant = self._itinf_quant_of(n, [r["step_chosen"] for r in control], rd_lambda)
+            self._set_itinf_quant(quant)
+            ks = [0] * n if quant is None else quant["steps"]
+            lams = step_lambdas(self._rd_lambda, ks, rd_lambda)
+            lat_kw = dict(step=ks) if any(ks) else {}
+            cost_kw = dict(lat_kw, lam=lams)                              # J at each image's own step and weight
+
+        def cost_of(latents):
+            return self.coded_cost(x, latents, **cost_kw)
+
         with torch.cuda.device(self.device):
-            start = self.coded_cost(x, self.latent_rvs)
+            start = cost_of(self.latent_rvs)
             best = [rv.loc.clone() for rv in self.latent_rvs.uq]
             j_best, bits_best, step_best = start["J"].copy(), start["bits"].copy(), np.zeros(n, np.int64)
+            met = None if budgets is None else np.array([r["met"] for r in control], bool)
             for done in range(1, steps + 1):
                 self.itinf_train_step(x, seed=seed, fetch=False)
                 if done != steps and (check_every is None or done % int(check_every)):
                     continue
-                cand = self.coded_cost(x, self.latent_rvs)
-                for i in np.nonzero(cand["J"] < j_best)[0]:           # strictly better only: the encoder's latents win a tie
+                cand = cost_of(self.latent_rvs)
+                # strictly better only: the encoder's latents win a tie
+                for i in np.nonzero(candidate_wins(cand["J"], cand["bits"], j_best, bits_best, budgets, flushed, met))[0]:
                     for keep, rv in zip(best, self.latent_rvs.uq):
                         keep[i].copy_(rv.loc[i])
                     j_best[i], bits_best[i], step_best[i] = cand["J"][i], cand["bits"][i], done
-            blob = codec.compress_latents(*best, x.shape[1:3])
+            blob = codec.compress_latents(*best, x.shape[1:3], **lat_kw)
         self.last_compress_latents = LatentRVCollection(uq=tuple(UQLatentRV(t) for t in best))
         self.last_compress_report = [dict(step_chosen=int(step_best[i]), J_start=float(start["J"][i]), J_chosen=float(j_best[i]),
                                           bits_start=float(start["bits"][i]), bits_chosen=float(bits_best[i])) for i in range(n)]
+        if stepped:
+            for i, r in enumerate(self.last_compress_report):
+                r.update(quant_step=int(ks[i]), lam=float(lams[i]))
+                if budgets is not None:
+                    r.update(budget_bits=float(budgets[i]), met=bool(met[i]))
         return blob
 
     def compress_many(self, xs):
@@ -772,11 +861,17 @@ class Model:
         return metrics
 
     # -- iterative inference (reference :389-413, common/itinf_lib.py:26-93) ----------------------------
-    def initialize_itinf(self, image_batch):
-        """latent_rvs = trainable copy of the encoder's latents; fresh Adam state (:389-395)."""
+    def initialize_itinf(self, image_batch, step=None, rd_lambda=None):
+        """latent_rvs = trainable copy of the encoder's latents; fresh Adam state (:389-395).
+        ``step`` (a ladder index, or one per image) / ``rd_lambda`` (a number, or one per image; default
+        lambda / step_size(k_i)^2): the steps that follow descend the loss at those quantisation steps,
+        mean_B(bits_i) / (H W) + (1 / n) sum_i lambda_i D_i (sga.SGAEngine.loss_and_grads(quant=...)).  Every index 0
+        and no ``rd_lambda``: the steps of before, launch for launch."""
         from ..sga import SGAEngine
         if self._optimizer_config.get("global_clipnorm") is not None:
             raise NotImplementedError("gradient clipping is not used by the reference's itinf config")
+        shape = tuple(image_batch.shape)
+        quant = self._itinf_quant_of(1 if len(shape) == 3 else shape[0], step, rd_lambda)    # every refusal before any launch
         if self._distortion == "ms_ssim":                               # ValueError where the loss is not computable
             ops.msssim_scale_sizes(*tuple(image_batch.shape)[1:3])
         self.latent_rvs = self.infer_latent_rvs(image_batch).get_trainable_copy()
@@ -785,6 +880,29 @@ class Model:
         self.itinf = True
         self._itinf_step = 0
         self._itinf_pending = None
+        self._set_itinf_quant(quant)
+
+    def _itinf_quant_of(self, n, step, rd_lambda):
+        """The host half of ``initialize_itinf(step=, rd_lambda=)``: the refusals, the ladder indexes and each image's lambda.
+        -> None (step 1 and the model's lambda for every image: the kernels of before) or dict(steps, lam)."""
+        if step is None and rd_lambda is None:
+            return None
+        from ..entropy_coding import check_steps
+        if self.factorized:
+            raise NotImplementedError("SGA at a quantisation step (step / rd_lambda): mean-scale hyperprior models only")
+        if self._precision != "fp32":
+            raise NotImplementedError(f"SGA at a quantisation step runs in precision 'fp32', not {self._precision!r}")
+        ks = check_steps(0 if step is None else step, n)
+        lams = step_lambdas(self._rd_lambda, ks, rd_lambda)             # iterative inference runs at the model's own lambda
+        return dict(steps=ks, lam=lams) if any(ks) or rd_lambda is not None else None
+
+    def _set_itinf_quant(self, quant):
+        if quant is not None:
+            from ..entropy_coding import step_tensors
+            with torch.cuda.device(self.device):
+                dweight = ops.to_device(quant["lam"] / float(self._rd_lambda), self.device)   # the distortion gradient is launched
+                quant["tensors"] = tuple(step_tensors(quant["steps"], self.device)) + (dweight,)    # with the scalar lambda
+        self._itinf_quant = quant
 
     @property
     def itinf_trainable_variables(self):
@@ -806,11 +924,13 @@ class Model:
         tau = cfg["tau"]
         lr = self._scheduled_lr
         locs = [rv.loc for rv in self.latent_rvs.uq]                     # (z_loc, y_loc); the factorized model: (y_loc,)
+        q = getattr(self, "_itinf_quant", None)
         with torch.cuda.device(self.device):
+            quant = None if q is None else q["tensors"]
             r = self._sga.loss_and_grads(x, locs[0] if len(locs) == 2 else None, locs[-1], tau, self._scheduled_rd_lambda,
                                          step=self._itinf_step, seed=seed,
                                          noise_z=None if noise is None else noise[0],
-                                         noise_y=None if noise is None else noise[-1])
+                                         noise_y=None if noise is None else noise[-1], **({} if quant is None else dict(quant=quant)))
             t = self._itinf_step + 1
             grads = [r["g_z"], r["g_y"]] if len(locs) == 2 else [r["g_y"]]
             for p, g, st in zip(locs, grads, self._adam):
@@ -819,7 +939,8 @@ class Model:
             # the metrics depend on (step, lr, lambda, tau) of THIS step: keep them with the device scalars
             rows = [r["bits_z"], r["bits_y"], r["sse"]] + ([r["msssim"]] if "msssim" in r else [])
             self._itinf_pending = dict(dev=torch.stack(rows), shape=tuple(x.shape), two=len(locs) == 2,
-                                       scalars=(self._scheduled_lr, self._scheduled_rd_lambda, tau))
+                                       scalars=(self._scheduled_lr, self._scheduled_rd_lambda, tau),
+                                       lams=None if q is None else q["lam"])
         self._itinf_step += 1
         self.last_grads = tuple(grads)
         return self.itinf_last_metrics() if fetch else None
@@ -834,7 +955,7 @@ class Model:
             host = pend["dev"].cpu().numpy()
             ops.check_conv_status()
         _, metrics = self._finish_metrics(pend["shape"], host[0] if pend["two"] else None, host[1], host[2],
-                                          msssim=host[3] if len(host) > 3 else None, sched=pend["scalars"])
+                                          msssim=host[3] if len(host) > 3 else None, sched=pend["scalars"], lams=pend.get("lams"))
         return metrics
 
     def itinf_validation_step(self, image_batch, training=False) -> Metrics:

@@ -1335,6 +1335,57 @@ def sga_normal_bwd(g_ytilde, sprime, dbits_dv, dbits_draw, weight):
     return g_y, g_h
 
 
+def _check_quant(quant, count, n, device):
+    """``quant`` = per-image device tensors (step float32, inv_step float32, shift int32[, dweight float32]) of the step-aware
+    SGA kernels (entropy_coding.step_tensors makes the first three): ``count`` of them, n entries each."""
+    if not isinstance(quant, (tuple, list)) or len(quant) < count:
+        raise ValueError(f"quant: a tuple of {count} per-image device tensors (step, inv_step, shift, dweight)")
+    quant = tuple(quant[:count])
+    for t, dt in zip(quant, (torch.float32, torch.float32, torch.int32, torch.float32)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.numel() == n and t.is_contiguous() and t.device == device):
+            raise ValueError(f"quant: one contiguous {dt} entry per image on {device} ({n} images): step / inv_step float32, "
+                             "shift int32, dweight float32")
+    return quant
+
+
+def sga_normal_step_fwd(y_loc, hyper, tau, quant, noise=None, seed=0, step=0):
+    """``sga_normal_fwd`` at one quantisation step per image: ``quant`` = (step_size, inv_step, shift[, dweight]) as
+    entropy_coding.step_tensors makes them; ``step`` stays the SGA step number of the generator.
+    -> (y_tilde = fma(step_size, v, mu), sprime = d v / d u, dbits_dv, dbits_draw, bits[n]), v the sample on the step's grid."""
+    _check_nhwc(y_loc)
+    c = y_loc.shape[-1]
+    _check_nhwc(hyper, 2 * c)
+    n, hw = y_loc.shape[0], y_loc.shape[1] * y_loc.shape[2]
+    if tuple(hyper.shape[:3]) != tuple(y_loc.shape[:3]):
+        raise ValueError(f"hyper-synthesis output {tuple(hyper.shape)} does not match latents {tuple(y_loc.shape)}")
+    if noise is not None and not (isinstance(noise, torch.Tensor) and noise.is_cuda and noise.dtype == torch.float32
+                                  and noise.is_contiguous() and tuple(noise.shape) == tuple(y_loc.shape) + (2,)):
+        raise ValueError("noise: contiguous float32 Gumbel pairs shaped like y_loc + (2,)")
+    st, inv, sh = _check_quant(quant, 3, n, y_loc.device)
+    yt, sp, dv, dr = (torch.empty_like(y_loc) for _ in range(4))
+    bits = torch.empty((n,), dtype=torch.float64, device=y_loc.device)
+    capi.call("sntc_sga_normal_step_fwd", _ptr(y_loc), _ptr(hyper), n, hw, c, float(tau), _ptr(noise), int(seed), int(step),
+              _ptr(st), _ptr(inv), _ptr(sh), _ptr(yt), _ptr(sp), _ptr(dv), _ptr(dr), _ptr(bits), _stream())
+    return yt, sp, dv, dr, bits
+
+
+def sga_normal_step_bwd(g_ytilde, sprime, dbits_dv, dbits_draw, weight, quant):
+    """``sga_normal_bwd`` at one quantisation step per image, ``quant`` = (step_size, inv_step, shift, dweight): dweight[i]
+    multiplies image i's distortion gradient.  -> (g_yloc, g_hyper[.., 2C])."""
+    _check_nhwc(g_ytilde)
+    n, h, w, c = g_ytilde.shape
+    for t in (sprime, dbits_dv, dbits_draw):
+        _check_nhwc(t, c)
+        if tuple(t.shape) != tuple(g_ytilde.shape):
+            raise ValueError(f"sga_normal_step_bwd: {tuple(t.shape)} does not match the gradient {tuple(g_ytilde.shape)}")
+    st, inv, _, dw = _check_quant(quant, 4, n, g_ytilde.device)
+    g_y = torch.empty_like(g_ytilde)
+    g_h = torch.empty((n, h, w, 2 * c), dtype=torch.float32, device=g_ytilde.device)
+    capi.call("sntc_sga_normal_step_bwd", _ptr(g_ytilde), _ptr(sprime), _ptr(dbits_dv), _ptr(dbits_draw), float(weight),
+              n, h * w, c, _ptr(st), _ptr(inv), _ptr(dw), _ptr(g_y), _ptr(g_h), _stream())
+    return g_y, g_h
+
+
 def sga_chain(g, dbits, sprime, weight):
     out = torch.empty_like(g)
     capi.call("sntc_sga_chain", _ptr(g), _ptr(dbits), _ptr(sprime), float(weight), g.numel(), _ptr(out), _stream())

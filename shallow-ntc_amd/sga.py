@@ -138,8 +138,15 @@ class SGAEngine:
             self.hyper = None if model.factorized else GradChain(model._hyper_synthesis)
             self.syn = make_backward(model._synthesis)
 
-    def loss_and_grads(self, x, z_loc, y_loc, tau, rd_lambda, step=0, seed=0, noise_z=None, noise_y=None):
+    def loss_and_grads(self, x, z_loc, y_loc, tau, rd_lambda, step=0, seed=0, noise_z=None, noise_y=None, quant=None):
+        """``quant`` = (step_size, inv_step, shift, dweight), one entry per image on the device (entropy_coding.step_tensors and
+        lambda_i / rd_lambda): the loss at a quantisation step, mean_B(bits_i) / (H W) + (1 / n) sum_i lambda_i D_i with y - mu on
+        the step's grid and the rate under the table shift places down the ladder.  The distortion gradient is
+        launched with the scalar ``rd_lambda``; the backward pass is linear in it, so lambda_i enters as dweight in the one
+        step-aware backward kernel.  None: step 1, the launches of before."""
         m = self.m
+        if quant is not None and m.factorized:
+            raise NotImplementedError("SGA at a quantisation step: mean-scale hyperprior models only")
         n, h, w, c = x.shape
         w_bpp = 1.0 / (n * h * w)                                      # bpp = mean_B(bits) / (H W)   (:302-307)
         scale = rd_lambda * 2.0 * 255.0 * 255.0 / (n * h * w * c)     # d(lambda * mean_B mean_HWC (255 d)^2)/d x_hat
@@ -160,11 +167,17 @@ class SGAEngine:
                         y_tilde=y_t, **extra)
         z_t, sp_z, dbz, bits_z = ops.sga_factorized_fwd(m._get_prior(), z_loc, tau, noise_z, seed, step)     # :262-268
         hyper, acts = self.hyper.forward(z_t)                                                              # :273
-        y_t, sp_y, dv, dr, bits_y = ops.sga_normal_fwd(y_loc, hyper, tau, noise_y, seed, step)             # :285-291
+        if quant is None:
+            y_t, sp_y, dv, dr, bits_y = ops.sga_normal_fwd(y_loc, hyper, tau, noise_y, seed, step)         # :285-291
+        else:
+            y_t, sp_y, dv, dr, bits_y = ops.sga_normal_step_fwd(y_loc, hyper, tau, quant, noise_y, seed, step)
         recon, cache = self.syn.forward(y_t)
         g_x, sse = distortion_grad(recon)                                                                  # :313-317,343
         g_yt = self.syn.backward(g_x, cache)
-        g_y, g_hyper = ops.sga_normal_bwd(g_yt, sp_y, dv, dr, w_bpp)
+        if quant is None:
+            g_y, g_hyper = ops.sga_normal_bwd(g_yt, sp_y, dv, dr, w_bpp)
+        else:
+            g_y, g_hyper = ops.sga_normal_step_bwd(g_yt, sp_y, dv, dr, w_bpp, quant)
         g_zt = self.hyper.backward(g_hyper, acts)
         g_z = ops.sga_chain(g_zt, dbz, sp_z, w_bpp)
         return dict(bits_z=bits_z, bits_y=bits_y, sse=sse, g_z=g_z, g_y=g_y, recon=recon, z_tilde=z_t, y_tilde=y_t, **extra)
