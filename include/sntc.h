@@ -564,6 +564,28 @@ int sntc_step_ladder_cost(const float* y, const float* mu, int n, int64_t hw, in
                           const float* inv_step, const int32_t* shift, int nsteps, const uint32_t* meta, int ntables,
                           int total_entries, const uint32_t* cost_q, uint64_t* cost, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The same three rules with the ladder index varying per latent POSITION (csrc/quant_step_map.hip; region-of-interest coding,
+ *   wire format 7): kmap int8 [n][hw], one index k in [-32, 32] per position, shared by its c channels.  step / inv_step come
+ *   from ONE table the host uploads, lut float [2][65]: lut[k + 32] = float32(r^k), lut[65 + k + 32] = float32(r^-k) (float64,
+ *   rounded once; never recomputed on the device).  The kernels clamp every index they read into [-32, 32]: no byte of a map
+ *   can read outside lut.  With a constant map: the per-image entry points above at that index, bit for bit.
+ *   Sizes and alignment as above (checked).
+ * ------------------------------------------------------------------------------------------------------- */
+int sntc_step_map_symbols(const float* y, const float* mu, int n, int64_t hw, int c, int mu_stride, const uint16_t* base_ids,
+                          const int8_t* kmap, const float* lut, int32_t* symbols, uint16_t* table_ids, void* stream);
+/* The decoder's half: table_ids = clamp(base_ids - kmap[image][position], 0, 63), [n][hw][c]. */
+int sntc_step_map_table_ids(const uint16_t* base_ids, int n, int64_t hw, int c, const int8_t* kmap, uint16_t* table_ids,
+                            void* stream);
+int sntc_dequant_step_map(const int32_t* symbols, const float* mu, int n, int64_t hw, int c, int mu_stride, const int8_t* kmap,
+                          const float* lut, float* y_hat, void* stream);
+/* sntc_step_ladder_cost over a map: candidate j (base int32 [nsteps] on the device, 1 <= nsteps <= 16) prices position p at
+ *   the index clamp(base[j] + offsets[image][p], -32, 32); offsets int8 [n][hw].  cost uint64 [n][nsteps], zeroed by the call.
+ *   One pass over y, mu and the ids; integer sums; the element-wise path for unaligned pointers, as there. */
+int sntc_step_map_ladder_cost(const float* y, const float* mu, int n, int64_t hw, int c, int mu_stride, const uint16_t* base_ids,
+                              const int8_t* offsets, const float* lut, const int32_t* base, int nsteps, const uint32_t* meta,
+                              int ntables, int total_entries, const uint32_t* cost_q, uint64_t* cost, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * SSIM / MS-SSIM statistics (eval-only quality metrics, reference mshyper/models.py:321-336 ->
  *   tf.image.ssim / tf.image.ssim_multiscale).  Images are float NHWC holding pixel

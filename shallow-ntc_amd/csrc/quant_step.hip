@@ -6,7 +6,8 @@
 //   symbol    s = (int)rintf((y - mu) * inv_step)            float32 subtract, then float32 multiply
 //   table id  t = clamp(t0 - k, 0, 63)                       t0 = sntc_scale_table_ids; off the ladder's ends the end table stays
 //   value     y_hat = fmaf(step, (float)s, mu)
-// The symbol and value rules live in step_rules.h: SGA at a step (sga.hip) samples and dequantises with the same functions.
+// The rules live in step_rules.h: SGA at a step (sga.hip) samples and dequantises with the same functions, and quant_step_map.hip
+// applies all three with an index per latent position.
 // At k = 0 (step = inv_step = 1.0f) they are the symbols of sntc_entropy_scale_normal, the ids of sntc_scale_table_ids and the
 // values of sntc_dequant_mean, bit for bit.
 //
@@ -22,17 +23,12 @@
 
 namespace sntc {
 
-constexpr int kLadderTop = 63;                              // last table of the scale ladder (64 normal tables)
 constexpr int kLadderMax = 16;                              // candidate steps of one ladder launch (their sums live in registers)
 constexpr int kLadderThreads = 1024;
 constexpr int kLadderGrid = 512;                            // workgroups of a launch, about
 constexpr int kLadderLdsLimit = kRansLdsTotal;              // descriptors + cost_q staged in LDS up to here
 
 __device__ __forceinline__ int step_symbol(float y, float mu, float inv_step) { return step_round(step_diff(y, mu), inv_step); }
-
-__device__ __forceinline__ unsigned step_table_id(unsigned t0, int shift) {
-  return (unsigned)min(max((int)t0 - shift, 0), kLadderTop);
-}
 
 typedef int qs_i32x4 __attribute__((ext_vector_type(4)));
 typedef float qs_f32x4 __attribute__((ext_vector_type(4)));

@@ -20,6 +20,11 @@ Wire format v5 = v3 with version byte 5 and, between the header and the length f
   quantisation step on the scale ladder (``step_size``; STEP_MIN <= k <= STEP_MAX).  y - mu is quantised with the step r^k,
   r = exp(SCALE_FACTOR), and coded with the table k places down the ladder (sigma_i / r^k = sigma_(i-k): the same 64 tables serve every
   step; csrc/quant_step.hip).  Written only when some index is non-zero: all zero is the v3 blob, byte for byte.
+Wire format v7 = v3 with version byte 7 and, between the header and the length fields, u32 record count | the records: the ladder
+  index of EVERY latent position (all C channels of a position share it; region-of-interest coding, csrc/quant_step_map.hip) as
+  maximal runs in raster order, image after image, a record = i8 index | u16 run length 1 .. 65535 (``pack_runs``); a run never
+  crosses an image boundary.  Written only when some image's map really varies: constant maps are the v5 / v3 blob of those
+  indexes, byte for byte -- a file has one spelling.  Version 6 is not assigned and stays refused.
 
 The factorized-prior model (factorized/models.py) has ONE latent and no hyper-synthesis: ``FactorizedCodec``, wire format v4
   b"SNTC" u16 version (low byte 4; high byte = the arithmetic tag, as above) | u16 n | u32 H | u32 W | u16 C | u16 h | u16 w |
@@ -53,6 +58,11 @@ SCALE_FACTOR = (math.log(SCALE_MAX) - math.log(SCALE_MIN)) / (NUM_SCALES - 1.0)
 VERSION_STEP = 5                          # v3 + one signed byte per image: its quantisation step's index on the scale ladder
 STEP_MIN, STEP_MAX = -32, 32              # ladder indexes a file may carry (checked here; the kernels' id clamp absorbs any shift)
 LADDER_MAX = 16                           # candidate steps of one sntc_step_ladder_cost launch
+VERSION_MAP = 7                           # v3 + the ladder index of every latent position, run-length coded
+OFFSET_MIN, OFFSET_MAX = -64, 64          # ``step_offsets`` a caller may pass: enough to cross the whole ladder either way
+RUN_MAX = 65535                           # positions one record of a v7 map covers at the most
+RUN_RECORD = np.dtype([("k", "i1"), ("run", "<u2")])      # "<bH", 3 bytes
+MAP_RECORD_BITS = 8 * RUN_RECORD.itemsize
 
 
 def step_size(k):
@@ -95,22 +105,140 @@ def check_budgets(target_bpp, n):
     return t
 
 
-def select_steps(bits, budget_bits, steps):
+def select_steps(bits, budget_bits, steps, map_bits=None):
     """The rate-control rule, a pure function: ``bits`` [n, len(steps)] = what image i would pay at ladder index steps[j],
     ``budget_bits`` [n].  Per image the SMALLEST index (the finest step) whose bits fit the budget -- not the first fit found
     walking down from a coarse step: a row need not be monotone -- and STEP_MAX, met = False, where none fits.
-    -> list of dict(step_chosen, bits_predicted, budget_bits, met)."""
+    ``map_bits`` [n] (rate control over ``step_offsets``): what image i's map of ladder indexes costs in the file, the same at
+    every candidate; it is added to every entry of the row before the comparison and reported.
+    -> list of dict(step_chosen, bits_predicted, budget_bits, met[, map_bits])."""
     bits = np.asarray(bits, np.float64)
     steps = [int(k) for k in steps]
     if bits.ndim != 2 or bits.shape[1] != len(steps) or len(budget_bits) != bits.shape[0]:
         raise ValueError("select_steps: bits [n, len(steps)] and n budgets")
+    if map_bits is not None:
+        map_bits = np.asarray(map_bits, np.float64)
+        if map_bits.shape != (bits.shape[0],):
+            raise ValueError("select_steps: one map_bits per image")
+        bits = bits + map_bits[:, None]
     out = []
-    for row, budget in zip(bits, budget_bits):
+    for i, (row, budget) in enumerate(zip(bits, budget_bits)):
         fits = [k for k, b in zip(steps, row) if b <= budget]
         k = min(fits) if fits else STEP_MAX
         pred = float(row[steps.index(k)]) if k in steps else float("nan")
         out.append(dict(step_chosen=k, bits_predicted=pred, budget_bits=float(budget), met=bool(fits)))
+        if map_bits is not None:
+            out[-1]["map_bits"] = float(map_bits[i])
     return out
+
+
+def check_offsets(step_offsets, n, h, w):
+    """``step_offsets`` of the public entry points -> C-contiguous int8 [n, h, w] (h, w: the latent resolution,
+    ``Codec.latent_shapes``); ValueError on a wrong shape, non-integers, bools, or values outside [OFFSET_MIN, OFFSET_MAX]."""
+    if isinstance(step_offsets, torch.Tensor):
+        step_offsets = step_offsets.detach().cpu().numpy()
+    a = np.asarray(step_offsets)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"step_offsets must be integers (offsets on the scale ladder), not {a.dtype}")
+    if a.shape != (n, h, w):
+        raise ValueError(f"step_offsets of shape {a.shape}: one offset per latent position, {(n, h, w)}")
+    if a.size and not (OFFSET_MIN <= int(a.min()) and int(a.max()) <= OFFSET_MAX):
+        raise ValueError(f"step_offsets outside [{OFFSET_MIN}, {OFFSET_MAX}]")
+    return np.ascontiguousarray(a, dtype=np.int8)
+
+
+def index_map(steps, offsets):
+    """K[i, p] = clip(step_i + step_offsets[i, p], STEP_MIN, STEP_MAX): the absolute ladder index of every position, int8 like
+    ``offsets`` ([n, h, w], ``check_offsets``); ``steps``: n ladder indexes."""
+    base = np.asarray(steps, np.int64).reshape(-1, 1, 1)
+    return np.clip(base + offsets.astype(np.int64), STEP_MIN, STEP_MAX).astype(np.int8)
+
+
+def uniform_steps(kmap):
+    """The per-image ladder indexes of a map whose every image is constant (the file is then v5 / v3), else None."""
+    flat = kmap.reshape(kmap.shape[0], -1)
+    return flat[:, 0].astype(np.int64).tolist() if (flat == flat[:, :1]).all() else None
+
+
+def count_runs(a):
+    """Maximal runs of equal values per image of ``a`` [n, ...], raster order -> int64 [n]."""
+    flat = np.asarray(a).reshape(len(a), -1)
+    return 1 + (flat[:, 1:] != flat[:, :-1]).sum(axis=1).astype(np.int64)
+
+
+def pack_runs(K) -> bytes:
+    """The absolute maps K (int8 [n, h w], raster order, image-major) as records ``<bH`` = (ladder index, run length 1 .. 65535).
+    Runs are maximal (neighbouring equal values merge) but never cross an image boundary; a run above 65535 is split into full
+    records and a remainder.  One spelling per map."""
+    K = np.asarray(K)
+    if K.ndim != 2 or K.dtype != np.int8 or K.shape[1] < 1:
+        raise ValueError("pack_runs: int8 [n, h * w]")
+    if K.size and not (STEP_MIN <= int(K.min()) and int(K.max()) <= STEP_MAX):
+        raise ValueError(f"ladder index outside [{STEP_MIN}, {STEP_MAX}]")
+    ks, runs = [], []
+    hw = K.shape[1]
+    for row in K:
+        starts = np.concatenate([[0], np.flatnonzero(row[1:] != row[:-1]) + 1])
+        lens = np.diff(np.concatenate([starts, [hw]]))
+        pieces = -(-lens // RUN_MAX)                                  # records per run
+        k = np.repeat(row[starts], pieces)
+        r = np.full(len(k), RUN_MAX, np.int64)
+        r[np.cumsum(pieces) - 1] = lens - (pieces - 1) * RUN_MAX      # the last record of each run takes the remainder
+        ks.append(k)
+        runs.append(r)
+    rec = np.empty(sum(len(k) for k in ks), RUN_RECORD)
+    rec["k"], rec["run"] = np.concatenate(ks), np.concatenate(runs)
+    return rec.tobytes()
+
+
+def parse_runs(buf, n, hw):
+    """The records of ``pack_runs`` -> K int8 [n, hw].  Refused (ERR_BAD_SHAPE): an index outside the ladder, a zero run, a run
+    crossing an image boundary, records that do not sum to hw for every image."""
+    bad = lambda what: capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream header: step map {what}")
+    if len(buf) % RUN_RECORD.itemsize:
+        raise bad("is not a whole number of records")
+    rec = np.frombuffer(buf, RUN_RECORD)
+    k, run = rec["k"], rec["run"].astype(np.int64)
+    if len(rec) and not (STEP_MIN <= int(k.min()) and int(k.max()) <= STEP_MAX):
+        raise bad(f"holds a quantisation step index outside [{STEP_MIN}, {STEP_MAX}]")
+    if (run == 0).any():
+        raise bad("holds a run of length 0")
+    ends = np.cumsum(run)
+    if not len(rec) or int(ends[-1]) != n * hw:
+        raise bad(f"covers {int(ends[-1]) if len(rec) else 0} positions, the latents have {n} x {hw}")
+    if not np.isin(np.arange(1, n + 1, dtype=np.int64) * hw, ends).all():
+        raise bad("has a run that crosses an image boundary")
+    return np.repeat(k, run).reshape(n, hw)
+
+
+def roi_offsets(mask, factor, inside=0, outside=12, grow=1, latent_hw=None):
+    """A boolean pixel mask [n, H, W] (True = region of interest) -> ``step_offsets`` int8 [n, h, w]: ``inside`` where the
+    position's factor x factor block of the padded image meets the mask, after the inside set has been dilated by ``grow``
+    positions (8-neighbourhood: the synthesis reads neighbouring positions), ``outside`` elsewhere.  The image is padded
+    bottom / right and the padding is cropped after decoding, so the mask is False there.  ``factor``: pixels per latent
+    position (16 for the models here); ``latent_hw`` = ``Model.step_offsets_shape(H, W)`` where the model pads the image beyond the
+    next multiple of ``factor`` (default: ceil(H / factor), ceil(W / factor))."""
+    mask = np.asarray(mask)
+    factor, grow = int(factor), int(grow)
+    if mask.ndim != 3 or mask.dtype != np.bool_ or factor < 1 or grow < 0:
+        raise ValueError("roi_offsets: a boolean mask [n, H, W], factor >= 1, grow >= 0")
+    for v in (inside, outside):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not OFFSET_MIN <= int(v) <= OFFSET_MAX:
+            raise ValueError(f"roi_offsets: inside / outside are ints in [{OFFSET_MIN}, {OFFSET_MAX}]")
+    n, H, W = mask.shape
+    h, w = (-(-H // factor), -(-W // factor)) if latent_hw is None else (int(latent_hw[0]), int(latent_hw[1]))
+    if h * factor < H or w * factor < W:
+        raise ValueError(f"roi_offsets: {h} x {w} positions of {factor} pixels do not cover a {H} x {W} image")
+    padded = np.zeros((n, h * factor, w * factor), np.bool_)
+    padded[:, :H, :W] = mask
+    roi = padded.reshape(n, h, factor, w, factor).any(axis=(2, 4))
+    for _ in range(grow):
+        wide = np.zeros((n, h + 2, w + 2), np.bool_)
+        for dy in range(3):
+            for dx in range(3):
+                wide[:, dy:dy + h, dx:dx + w] |= roi
+        roi = wide[:, 1:-1, 1:-1]
+    return np.where(roi, np.int8(inside), np.int8(outside)).astype(np.int8)
 
 
 def quantize_pmf(pmf, escape_mass):
@@ -487,6 +615,69 @@ def step_ladder_cost(y, hyper, base_ids, steps, tables: DeviceTables, tensors=No
     return cost
 
 
+def step_lut(device):
+    """What the step-map kernels (csrc/quant_step_map.hip) look steps up in: float32 [2, 65] on ``device``, row 0 =
+    step_size(k), row 1 = step_size(-k), column k - STEP_MIN (``step_size``: float64, rounded once)."""
+    ks = range(STEP_MIN, STEP_MAX + 1)
+    return torch.from_numpy(np.array([[step_size(k) for k in ks], [step_size(-k) for k in ks]], np.float32)).to(device)
+
+
+def _check_map(kmap, like, what):
+    n, h, w = like.shape[:3]
+    if not isinstance(kmap, torch.Tensor) or kmap.dtype != torch.int8 or tuple(kmap.shape) != (n, h, w) or not kmap.is_contiguous() \
+            or kmap.device != like.device:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"{what}: one int8 ladder index per latent position, [{n}, {h}, {w}] on the latents' device")
+
+
+def _check_lut(lut, like, what):
+    if not isinstance(lut, torch.Tensor) or lut.dtype != torch.float32 or tuple(lut.shape) != (2, STEP_MAX - STEP_MIN + 1) \
+            or not lut.is_contiguous() or lut.device != like.device:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"{what}: lut = step_lut(device)")
+
+
+def step_map_table_ids(base_ids, kmap):
+    """``scale_table_ids`` shifted down the ladder per POSITION: clamp(id - kmap[image, position], 0, 63); ``base_ids`` int16
+    storage [n, h, w, c], ``kmap`` int8 [n, h, w] on the device.  What the decoder of a v7 blob indexes its tables with."""
+    if base_ids.dtype != torch.int16 or base_ids.dim() != 4 or not base_ids.is_contiguous():
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_map_table_ids: contiguous int16 (uint16 storage) ids [n, h, w, c]")
+    _check_map(kmap, base_ids, "step_map_table_ids")
+    n, h, w, c = base_ids.shape
+    out = torch.empty_like(base_ids)
+    capi.call("sntc_step_map_table_ids", _p(base_ids), n, h * w, c, _p(kmap), _p(out), ops._stream())
+    return out
+
+
+def step_map_ladder_cost(y, hyper, base_ids, offsets, bases, tables: DeviceTables, lut=None, bases_d=None):
+    """``step_ladder_cost`` over a map: candidate j prices position p at the ladder index clip(bases[j] + offsets[image, p],
+    STEP_MIN, STEP_MAX); ``offsets`` int8 [n, h, w] on the device, ``bases`` ladder indexes shared by the batch.
+    -> int64 [n, len(bases)] on the device, 2^-16 bit.  ``lut``: ``step_lut(device)``, ``bases_d``: ``bases`` as int32 on the device,
+    if the caller keeps them (else one small upload each)."""
+    c = y.shape[-1]
+    if y.dtype != torch.float32 or hyper.dtype != torch.float32 or base_ids.dtype != torch.int16 or y.dim() != 4 or hyper.dim() != 4 \
+            or tuple(hyper.shape[:3]) != tuple(y.shape[:3]) or hyper.shape[-1] not in (c, 2 * c) or tuple(base_ids.shape) != tuple(y.shape) \
+            or not (y.is_contiguous() and hyper.is_contiguous() and base_ids.is_contiguous()):
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_map_ladder_cost: y float32 [n, h, w, c], hyper [n, h, w, c or 2 c], ids int16 like y, contiguous")
+    _check_map(offsets, y, "step_map_ladder_cost")
+    bases = check_steps(list(bases), len(bases))
+    if not bases:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_map_ladder_cost: no candidate step")
+    lut = step_lut(y.device) if lut is None else lut
+    _check_lut(lut, y, "step_map_ladder_cost")
+    n, hw = y.shape[0], y.shape[1] * y.shape[2]
+    base_d = torch.tensor(bases, dtype=torch.int32).to(y.device) if bases_d is None else bases_d
+    if base_d.dtype != torch.int32 or tuple(base_d.shape) != (len(bases),) or not base_d.is_contiguous() or base_d.device != y.device:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_map_ladder_cost: bases_d = the candidates as int32 on the latents' device")
+    cost = torch.empty((n, len(bases)), dtype=torch.int64, device=y.device)
+    for lo in range(0, len(bases), LADDER_MAX):
+        k = min(LADDER_MAX, len(bases) - lo)
+        part = cost if k == len(bases) else torch.empty((n, k), dtype=torch.int64, device=y.device)
+        capi.call("sntc_step_map_ladder_cost", _p(y), _p(hyper), n, hw, c, hyper.shape[-1], _p(base_ids), _p(offsets), _p(lut),
+                  _p(base_d[lo:lo + k]), k, _p(tables.meta), tables.ntables, tables.total, _p(tables.cost_q), _p(part), ops._stream())
+        if part is not cost:
+            cost[:, lo:lo + k] = part
+    return cost
+
+
 def channel_table_ids(shape, device):
     n, h, w, c = shape
     tid = torch.empty((n, h, w, c), dtype=torch.int16, device=device)
@@ -506,7 +697,7 @@ def int_to_float(x):
     return out
 
 
-# -- wire formats v3 / v5: pure host functions (numbers in, numbers out; no device) ----------------------------------------
+# -- wire formats v3 / v5 / v7: pure host functions (numbers in, numbers out; no device) ----------------------------------------
 HEAD_V3 = "<HHIIHHHHHHHHBB"               # version | n | H | W | C | Cz | hz | wz | h | w | segments_z | segments_y | lanes_z | lanes_y
 
 
@@ -523,10 +714,9 @@ def pack_v3(arith, n, H, W, dims, sz, sy, lz, ly, zl, yl, steps=None) -> bytes:
     return head + np.asarray(zl, np.int64).astype("<u4").tobytes() + np.asarray(yl, np.int64).astype("<u4").tobytes()
 
 
-def parse_v3(blob: bytes, precision, latent_shapes):
-    """Header and stream lengths of one v3 / v5 blob, checked against the decoding model: ``precision`` its arithmetic,
-    ``latent_shapes(H, W) -> (C, Cz, hz, wz, h, w)`` its latents for an H x W image.  -> dict(..., steps = the n ladder indexes of
-    a v5 blob or None, pos = payload offset)."""
+def _parse_head(blob, precision, latent_shapes, versions):
+    """The checks every hyperprior format shares, up to the end of the fixed header: magic, version (one of ``versions``),
+    arithmetic, and every dimension recomputed from (H, W) and the decoding model.  -> (version byte, dict of the fields, pos)."""
     if blob[:4] != MAGIC:
         raise capi.SntcError(capi.ERR_BAD_SHAPE, "not an SNTC bitstream")
     pos = 4 + struct.calcsize(HEAD_V3)
@@ -534,7 +724,7 @@ def parse_v3(blob: bytes, precision, latent_shapes):
         raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
     ver, n, H, W, c, cz, hz, wz, h, w, sz, sy, lz, ly = struct.unpack_from(HEAD_V3, blob, 4)
     arith, ver = ver >> 8, ver & 0xff
-    if ver not in (VERSION, VERSION_STEP):
+    if ver not in versions:
         raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream version {ver}")
     if arith != ARITH[precision]:
         names = {v: k for k, v in ARITH.items()}
@@ -551,15 +741,13 @@ def parse_v3(blob: bytes, precision, latent_shapes):
     ez, ey = hz * wz * cz, h * w * c
     if (sz, sy) != (_segments(ez), _segments(ey)) or (lz, ly) != (_lanes(-(-ez // sz)), _lanes(-(-ey // sy))):
         raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream header: segment / lane counts do not match the latent sizes")
-    steps = None
-    if ver == VERSION_STEP:
-        if len(blob) < pos + n:
-            raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
-        steps = np.frombuffer(blob, np.int8, n, pos).astype(np.int64).tolist()
-        pos += n
-        if not all(STEP_MIN <= k <= STEP_MAX for k in steps):
-            raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream header: quantisation step index outside [{STEP_MIN}, {STEP_MAX}]")
-    nz, ny = n * sz, n * sy
+    return ver, dict(n=n, H=H, W=W, c=c, cz=cz, hz=hz, wz=wz, h=h, w=w, sz=sz, sy=sy, lz=lz, ly=ly), pos
+
+
+def _parse_lengths(blob, hd, pos):
+    """The length fields at ``pos`` and the payload they announce: the blob must end where its streams do.  Fills zl, yl, pos
+    (= payload offset), zw, yw of ``hd``."""
+    nz, ny = hd["n"] * hd["sz"], hd["n"] * hd["sy"]
     if len(blob) < pos + 4 * (nz + ny):
         raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
     zl = np.frombuffer(blob, "<u4", nz, pos).astype(np.int64)
@@ -568,8 +756,66 @@ def parse_v3(blob: bytes, precision, latent_shapes):
     zw, yw = int(zl.sum()), int(yl.sum())
     if len(blob) != pos + 2 * (zw + yw):
         raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
-    return dict(n=n, H=H, W=W, c=c, cz=cz, hz=hz, wz=wz, h=h, w=w, sz=sz, sy=sy, lz=lz, ly=ly, zl=zl, yl=yl, pos=pos, zw=zw, yw=yw,
-                steps=steps)
+    hd.update(zl=zl, yl=yl, pos=pos, zw=zw, yw=yw)
+    return hd
+
+
+def parse_v3(blob: bytes, precision, latent_shapes):
+    """Header and stream lengths of one v3 / v5 blob, checked against the decoding model: ``precision`` its arithmetic,
+    ``latent_shapes(H, W) -> (C, Cz, hz, wz, h, w)`` its latents for an H x W image.  -> dict(..., steps = the n ladder indexes of
+    a v5 blob or None, pos = payload offset)."""
+    ver, hd, pos = _parse_head(blob, precision, latent_shapes, (VERSION, VERSION_STEP))
+    n = hd["n"]
+    steps = None
+    if ver == VERSION_STEP:
+        if len(blob) < pos + n:
+            raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+        steps = np.frombuffer(blob, np.int8, n, pos).astype(np.int64).tolist()
+        pos += n
+        if not all(STEP_MIN <= k <= STEP_MAX for k in steps):
+            raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream header: quantisation step index outside [{STEP_MIN}, {STEP_MAX}]")
+    hd = _parse_lengths(blob, hd, pos)
+    hd["steps"] = steps
+    return hd
+
+
+def pack_v7(arith, n, H, W, dims, sz, sy, lz, ly, zl, yl, kmap) -> bytes:
+    """Everything of a hyperprior blob in front of the payload when the ladder index varies per position: ``kmap`` int8
+    [n, h, w], absolute indexes.  Wire format 7 = the v3 header with version byte 7 | u32 record count | the records of
+    ``pack_runs`` | the v3 length fields.  The writer is canonical: where every image's map is constant this is ``pack_v3`` of
+    those indexes (v5; v3 if all are 0), byte for byte -- version 7 appears only for a map that really varies."""
+    c, cz, hz, wz, h, w = dims
+    kmap = np.asarray(kmap)
+    if kmap.dtype != np.int8 or kmap.shape != (n, h, w):
+        raise ValueError(f"pack_v7: kmap int8 {(n, h, w)}")
+    records = pack_runs(kmap.reshape(n, h * w))                      # ValueError on an index outside the ladder
+    steps = uniform_steps(kmap)
+    if steps is not None:
+        return pack_v3(arith, n, H, W, dims, sz, sy, lz, ly, zl, yl, steps)
+    head = MAGIC + struct.pack(HEAD_V3, VERSION_MAP | (arith << 8), n, H, W, c, cz, hz, wz, h, w, sz, sy, lz, ly)
+    head += struct.pack("<I", len(records) // RUN_RECORD.itemsize) + records
+    return head + np.asarray(zl, np.int64).astype("<u4").tobytes() + np.asarray(yl, np.int64).astype("<u4").tobytes()
+
+
+def parse_v7(blob: bytes, precision, latent_shapes):
+    """``parse_v3`` for a v7 blob: the same header, arithmetic and shape checks, then the step map.  Refused with ERR_BAD_SHAPE:
+    a record count above n h w, a short blob ("truncated"), and what ``parse_runs`` refuses.  -> the ``parse_v3`` dict with
+    steps = None and kmap = int8 [n, h, w]."""
+    _, hd, pos = _parse_head(blob, precision, latent_shapes, (VERSION_MAP,))
+    n, h, w = hd["n"], hd["h"], hd["w"]
+    if len(blob) < pos + 4:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+    (count,) = struct.unpack_from("<I", blob, pos)
+    pos += 4
+    if count > n * h * w:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream header: step map of {count} records for {n * h * w} positions")
+    size = count * RUN_RECORD.itemsize
+    if len(blob) < pos + size:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+    kmap = parse_runs(blob[pos:pos + size], n, h * w).reshape(n, h, w)
+    hd = _parse_lengths(blob, hd, pos + size)
+    hd.update(steps=None, kmap=np.ascontiguousarray(kmap))
+    return hd
 
 
 class Codec:
@@ -619,17 +865,50 @@ class Codec:
         """``step_tensors`` of ladder indexes on the model's device (one small upload, on the current stream)."""
         return step_tensors(steps, self.m.device)
 
+    def _quant(self, step, step_offsets, n, H, W):
+        """``step`` / ``step_offsets`` of the public entry points -> (steps, kmap): (None, None) = today's path; (the n ladder
+        indexes, None) where every image's map K = clip(step_i + step_offsets[i], STEP_MIN, STEP_MAX) is constant (the per-image
+        kernels, wire format 5); else (None, K int8 [n, h, w]) (csrc/quant_step_map.hip, wire format 7).  Every refusal here:
+        before anything is enqueued."""
+        if step_offsets is None:
+            return self._steps(step, n), None
+        c, cz, hz, wz, h, w = self.latent_shapes(H, W)
+        offs = check_offsets(step_offsets, n, h, w)
+        ks = check_steps(0 if step is None else step, n)
+        if self.m._precision != "fp32":
+            raise NotImplementedError(f"quantisation steps run in precision 'fp32', not {self.m._precision!r}: the pre-split "
+                                      "dequantisation is not extended")
+        kmap = index_map(ks, offs)
+        ks = uniform_steps(kmap)
+        if ks is not None:
+            return (ks if any(ks) else None), None
+        return None, kmap
+
+    def _map_lut(self):
+        """``step_lut`` on the model's device, uploaded once."""
+        if getattr(self, "_lut", None) is None:
+            self._lut = step_lut(self.m.device)
+        return self._lut
+
+    def _map_tensor(self, kmap):
+        """A host map (absolute indexes or offsets, int8 [n, h, w]) on the model's device: one small upload."""
+        return torch.from_numpy(kmap).to(self.m.device)
+
     def _hyper_of(self, z):
         """z_loc -> (zi int32, the hyper-synthesis of it): what every step shares."""
         zi = round_to_int(z)
         return zi, self.m._hyper_synthesis(int_to_float(zi))
 
-    def _symbols(self, z, y, steps=None, pre=None):
+    def _symbols(self, z, y, steps=None, pre=None, kmap=None):
         """(z_loc, y_loc) -> what the file carries: (zi int32, z's table ids, y symbols int32, y's table ids, hyper).
-        ``steps``: None, or one ladder index per image (csrc/quant_step.hip); ``pre``: ``_hyper_of(z)`` if the caller has it."""
+        ``steps``: None, or one ladder index per image (csrc/quant_step.hip); ``kmap``: None, or one per position, int8
+        [n, h, w] on the device (csrc/quant_step_map.hip); ``pre``: ``_hyper_of(z)`` if the caller has it."""
         m = self.m
         zi, hyper = self._hyper_of(z) if pre is None else pre
         ztid = channel_table_ids(z.shape, m.device)
+        if kmap is not None:
+            sym, ytid = ops.step_map_symbols(y, hyper, scale_table_ids(hyper), kmap, self._map_lut())
+            return zi, ztid, sym, ytid, hyper
         if steps is None:
             _, _, sym = ops.entropy_scale_normal(y, hyper, want_symbols=True)
             return zi, ztid, sym, scale_table_ids(hyper), hyper
@@ -637,15 +916,16 @@ class Codec:
         sym, ytid = ops.step_symbols(y, hyper, scale_table_ids(hyper), inv, sh)
         return zi, ztid, sym, ytid, hyper
 
-    def _launch_latents(self, z, y, image_hw, steps=None, pre=None):
-        """The device half of ``compress_latents`` on the current stream, no host synchronisation."""
+    def _launch_latents(self, z, y, image_hw, steps=None, pre=None, kmap=None):
+        """The device half of ``compress_latents`` on the current stream, no host synchronisation.  ``kmap``: the host map of
+        ``_quant`` (it travels in the file)."""
         n, H, W = self._check_latents(z, y, image_hw)
-        zi, ztid, sym, ytid, _ = self._symbols(z, y, steps, pre)
+        zi, ztid, sym, ytid, _ = self._symbols(z, y, steps, pre, None if kmap is None else self._map_tensor(kmap))
         sz, sy = _segments(zi[0].numel()), _segments(sym[0].numel())
         lz, ly = _lanes(-(-zi[0].numel() // sz)), _lanes(-(-sym[0].numel() // sy))
         zs, zlen = rans_encode_launch(zi, ztid, self.z_tables, sz, lz)
         ys, ylen = rans_encode_launch(sym, ytid, self.y_tables, sy, ly)
-        return dict(n=n, H=H, W=W, z=z, y=y, sz=sz, sy=sy, lz=lz, ly=ly, zs=zs, zlen=zlen, ys=ys, ylen=ylen, steps=steps)
+        return dict(n=n, H=H, W=W, z=z, y=y, sz=sz, sy=sy, lz=lz, ly=ly, zs=zs, zlen=zlen, ys=ys, ylen=ylen, steps=steps, kmap=kmap)
 
     def _finish(self, jobs):
         """Launched jobs -> their blobs: the stream lengths of ALL jobs come back in one copy, the packed payloads in another."""
@@ -663,57 +943,69 @@ class Codec:
         for j in jobs:
             z, y = j["z"], j["y"]
             zw, yw = int(j["zl"].sum()), int(j["yl"].sum())
-            head = pack_v3(ARITH[m._precision], j["n"], j["H"], j["W"], (y.shape[-1], z.shape[-1], z.shape[1], z.shape[2], y.shape[1], y.shape[2]),
-                           j["sz"], j["sy"], j["lz"], j["ly"], j["zl"], j["yl"], j.get("steps"))
+            dims = (y.shape[-1], z.shape[-1], z.shape[1], z.shape[2], y.shape[1], y.shape[2])
+            fields = (ARITH[m._precision], j["n"], j["H"], j["W"], dims, j["sz"], j["sy"], j["lz"], j["ly"], j["zl"], j["yl"])
+            head = pack_v3(*fields, j.get("steps")) if j.get("kmap") is None else pack_v7(*fields, j["kmap"])
             out.append(head + words[o:o + zw + yw].tobytes())
             o += zw + yw
         return out
 
-    def compress_latents(self, z_loc, y_loc, image_hw, step=None) -> bytes:
+    def compress_latents(self, z_loc, y_loc, image_hw, step=None, step_offsets=None) -> bytes:
         """Latents of this model for images of ``image_hw`` = (H, W) -- the encoder's, or ones refined by iterative inference --
         -> the bitstream ``decompress`` reads: z is rounded, the hyper-synthesis gives mu / the scale indexes, y - mu is rounded,
         both are coded.  ``compress(x)`` is this on ``infer_latent_rvs(x)``.  ``step``: an index on the scale ladder, or one per
         image: y - mu is quantised with the step ``step_size(k)`` and coded with the tables k places down the ladder (wire
-        format 5; with every index 0 the v3 blob of ``step=None``, byte for byte)."""
+        format 5; with every index 0 the v3 blob of ``step=None``, byte for byte).  ``step_offsets``: integers [n, h, w] at latent
+        resolution, added to the image's step per position and clipped to the ladder (wire format 7 where the result varies
+        inside an image; a constant result is the v5 / v3 blob of those indexes, byte for byte)."""
         m = self.m
-        steps = self._steps(step, z_loc.shape[0])
+        steps, kmap = self._quant(step, step_offsets, z_loc.shape[0], int(image_hw[0]), int(image_hw[1]))
         with torch.cuda.device(m.device):
-            return self._finish([self._launch_latents(z_loc.contiguous(), y_loc.contiguous(), image_hw, steps)])[0]
+            return self._finish([self._launch_latents(z_loc.contiguous(), y_loc.contiguous(), image_hw, steps, kmap=kmap)])[0]
 
-    def latents_cost(self, z_loc, y_loc, x, step=None):
+    def latents_cost(self, z_loc, y_loc, x, step=None, step_offsets=None):
         """What ``compress_latents`` would write for these latents and what ``decompress`` would make of it, without writing it:
         -> (cost_z, cost_y int64 [n] in 2^-16 bit (``rans_cost``), uint8 pixels, integer SSE [n] against ``x``), all on the
-        device, no host synchronisation.  ``step`` as in ``compress_latents``."""
+        device, no host synchronisation.  ``step`` / ``step_offsets`` as in ``compress_latents``."""
         m = self.m
         n, H, W = self._check_latents(z_loc, y_loc, x.shape[1:3])
-        steps = self._steps(step, n)
-        zi, ztid, sym, ytid, hyper = self._symbols(z_loc.contiguous(), y_loc.contiguous(), steps)
+        steps, kmap = self._quant(step, step_offsets, n, H, W)
+        kmap = None if kmap is None else self._map_tensor(kmap)
+        zi, ztid, sym, ytid, hyper = self._symbols(z_loc.contiguous(), y_loc.contiguous(), steps, kmap=kmap)
         cost_z, cost_y = rans_cost(zi, ztid, self.z_tables), rans_cost(sym, ytid, self.y_tables)
-        if steps is not None:
+        if kmap is not None:
+            y_hat = ops.dequant_step_map(sym, hyper, kmap, self._map_lut())
+        elif steps is not None:
             y_hat = ops.dequant_step(sym, hyper, self._step_tensors(steps)[0])
         else:
             y_hat = ops.dequant_split3(sym, hyper) if m._synthesis.takes_s3(sym.shape[1], sym.shape[2]) else ops.dequant_scale_normal(sym, hyper)
         px, sse = m._pixels(y_hat, (H, W), x)                     # the decoder's own steps from the symbols on
         return cost_z, cost_y, px, sse
 
-    def _ladder(self, z, y, steps, pre=None):
+    def _ladder(self, z, y, steps, pre=None, offsets=None):
         zi, hyper = self._hyper_of(z) if pre is None else pre
         cost_z = rans_cost(zi, channel_table_ids(z.shape, self.m.device), self.z_tables)
-        cost_y = step_ladder_cost(y, hyper, scale_table_ids(hyper), steps, self.y_tables, self._step_tensors(steps))
+        if offsets is None:
+            cost_y = step_ladder_cost(y, hyper, scale_table_ids(hyper), steps, self.y_tables, self._step_tensors(steps))
+        else:
+            cost_y = step_map_ladder_cost(y, hyper, scale_table_ids(hyper), self._map_tensor(offsets), steps, self.y_tables, self._map_lut())
         return cost_z, cost_y
 
-    def ladder_cost(self, z_loc, y_loc, image_hw, steps):
+    def ladder_cost(self, z_loc, y_loc, image_hw, steps, step_offsets=None):
         """``latents_cost``'s (cost_z, cost_y) at EVERY ladder index of ``steps`` without forming a symbol tensor: -> (cost_z
         int64 [n], cost_y int64 [n, len(steps)]) in 2^-16 bit on the device, no host synchronisation.  y, mu and the scale
-        indexes are read once per launch of at most ``LADDER_MAX`` candidates (csrc/quant_step.hip)."""
+        indexes are read once per launch of at most ``LADDER_MAX`` candidates (csrc/quant_step.hip).  ``step_offsets`` (integers
+        [n, h, w]): candidate j prices position p at clip(steps[j] + step_offsets[i, p]) -- what ``latents_cost(step=steps[j],
+        step_offsets=...)`` returns (csrc/quant_step_map.hip)."""
         steps = check_steps(list(steps), len(steps))
         if not steps:
             raise ValueError("ladder_cost: no candidate step")
         if self.m._precision != "fp32":
             raise NotImplementedError(f"quantisation steps run in precision 'fp32', not {self.m._precision!r}")
-        self._check_latents(z_loc, y_loc, image_hw)
+        n, H, W = self._check_latents(z_loc, y_loc, image_hw)
+        offsets = None if step_offsets is None else check_offsets(step_offsets, n, *y_loc.shape[1:3])
         with torch.cuda.device(self.m.device):
-            return self._ladder(z_loc.contiguous(), y_loc.contiguous(), steps)
+            return self._ladder(z_loc.contiguous(), y_loc.contiguous(), steps, offsets=offsets)
 
     def flushed_bits(self, H, W):
         """The lane states every image's streams flush, in bits: 32 per lane and stream (in the file, not in ``rans_cost``)."""
@@ -722,8 +1014,11 @@ class Codec:
         sz, sy = _segments(ez), _segments(ey)
         return 32 * (sz * _lanes(-(-ez // sz)) + sy * _lanes(-(-ey // sy)))
 
-    def compress(self, x, step=None, target_bpp=None) -> bytes:
-        """``step``: as in ``compress_latents``.  ``target_bpp`` (a number, or one per image): rate control -- per image the
+    def compress(self, x, step=None, target_bpp=None, step_offsets=None) -> bytes:
+        """``step`` / ``step_offsets``: as in ``compress_latents``; with ``target_bpp`` the offsets are added to the index rate
+        control chooses, the candidates are priced over the map (``ladder_cost(..., step_offsets=...)``), and each image's
+        prediction counts ``map_bits`` = 24 per maximal run of its offsets (an upper bound on the records written: clipping
+        can only merge runs).  ``target_bpp`` (a number, or one per image): rate control -- per image the
         finest step of the whole ladder whose predicted bits (``ladder_cost`` + the flushed lane states; header and length
         fields not counted) are within target_bpp H W, STEP_MAX where none is.  One encoder pass, the ladder launches, one
         read-back, the coding launches.  ``last_report``: per image step_chosen, bits_predicted, budget_bits, met."""
@@ -732,31 +1027,38 @@ class Codec:
         n, H, W = x.shape[0], int(x.shape[1]), int(x.shape[2])
         if step is not None and target_bpp is not None:
             raise ValueError("compress: step and target_bpp exclude each other")
-        steps = self._steps(step, n)
-        budgets = None
+        steps, kmap = self._quant(step, step_offsets, n, H, W)
+        budgets, offsets = None, None
         if target_bpp is not None:
             budgets = check_budgets(target_bpp, n) * float(H * W)
             if m._precision != "fp32":
                 raise NotImplementedError(f"quantisation steps run in precision 'fp32', not {m._precision!r}")
+            if step_offsets is not None:
+                offsets = check_offsets(step_offsets, n, *self.latent_shapes(H, W)[4:])
+                offsets = offsets if offsets.any() else None          # all zero: today's rate control, launch for launch
         with torch.cuda.device(m.device):
             lat = m.infer_latent_rvs(x)
             z, y = lat.uq[0].loc.contiguous(), lat.uq[1].loc.contiguous()
             if budgets is None:
-                return self._finish([self._launch_latents(z, y, (H, W), steps)])[0]
-            self.last_report, pre = self._rate_control(z, y, H, W, budgets)
+                return self._finish([self._launch_latents(z, y, (H, W), steps, kmap=kmap)])[0]
+            self.last_report, pre = self._rate_control(z, y, H, W, budgets, offsets)
             chosen = [r["step_chosen"] for r in self.last_report]
-            return self._finish([self._launch_latents(z, y, (H, W), chosen if any(chosen) else None, pre)])[0]
+            steps, kmap = self._quant(chosen, offsets, n, H, W)
+            return self._finish([self._launch_latents(z, y, (H, W), steps, pre, kmap)])[0]
 
-    def _rate_control(self, z, y, H, W, budget_bits):
+    def _rate_control(self, z, y, H, W, budget_bits, offsets=None):
         """The rate-control pass of ``compress(x, target_bpp=...)`` on given latents: the whole ladder priced in one pass, the
-        flushed lane states counted, ``select_steps``.  -> (the per-image report, ``_hyper_of(z)`` for the coding launches)."""
+        flushed lane states counted, ``select_steps``.  ``offsets`` (``check_offsets``): the candidates are bases of the map
+        clip(base + offsets), and 24 bits per maximal run of an image's offsets are counted for its map.
+        -> (the per-image report, ``_hyper_of(z)`` for the coding launches)."""
         self._check_latents(z, y, (H, W))
         ladder = list(range(STEP_MIN, STEP_MAX + 1))
         pre = self._hyper_of(z)
-        cost_z, cost_y = self._ladder(z, y, ladder, pre)
+        cost_z, cost_y = self._ladder(z, y, ladder, pre, offsets)
         host = torch.cat([cost_z[:, None], cost_y], dim=1).cpu().numpy()                                         # the one read-back
         bits = (host[:, :1] + host[:, 1:]) / float(COST_UNIT) + float(self.flushed_bits(H, W))
-        return select_steps(bits, budget_bits, ladder), pre
+        map_bits = None if offsets is None else MAP_RECORD_BITS * count_runs(offsets)
+        return select_steps(bits, budget_bits, ladder, map_bits), pre
 
     def compress_many(self, xs):
         """``compress`` for several batches (e.g. one per image size of a set) -> their bitstreams, in order, byte for byte what one
@@ -786,9 +1088,11 @@ class Codec:
 
     def _parse(self, blob: bytes):
         """Header and stream lengths of one blob, checked against THIS model: nothing later trusts the header."""
-        hd = parse_v3(blob, self.m._precision, self.latent_shapes)
-        if hd["steps"] is not None and self.m._precision != "fp32":
-            raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream version {VERSION_STEP} (quantisation steps) decodes in precision 'fp32' only")
+        mapped = len(blob) > 4 and blob[4] == VERSION_MAP          # the version byte: 3 and 5 -> parse_v3, 7 -> parse_v7
+        hd = (parse_v7 if mapped else parse_v3)(blob, self.m._precision, self.latent_shapes)
+        hd.setdefault("kmap", None)
+        if (hd["steps"] is not None or mapped) and self.m._precision != "fp32":
+            raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream version {blob[4]} (quantisation steps) decodes in precision 'fp32' only")
         return hd
 
     def decompress(self, blob: bytes):
@@ -826,6 +1130,9 @@ class Codec:
             off_d, word_d = up[:8 * noff].view(torch.int64), up[8 * noff:].view(torch.int16)
             # v5: every blob's step tensors go up here too, before anything is enqueued; they are read on the caller's stream only
             stepd = [None if hd["steps"] is None else self._step_tensors(hd["steps"]) for hd in heads]
+            # v7: so do every blob's map and the step table the map kernels index
+            mapd = [None if hd["kmap"] is None else self._map_tensor(hd["kmap"]) for hd in heads]
+            lut = self._map_lut() if any(t is not None for t in mapd) else None
             pay, offd = [], []
             o = wpos = 0
             for hd in heads:
@@ -882,6 +1189,8 @@ class Codec:
                 tidl[k] = scale_table_ids(hyper)
                 if hd["steps"] is not None:      # v5: the tables k places down the ladder, the decoder's start tables unchanged
                     tidl[k] = step_table_ids(tidl[k], stepd[k][2])
+                if mapd[k] is not None:          # v7: the same shift per position
+                    tidl[k] = step_map_table_ids(tidl[k], mapd[k])
                 if piped:
                     launch_latents(k)
             if not piped:                    # A/B (PIPELINE_BLOBS = False), round 4's schedule: every hyper-synthesis, then every blob's
@@ -898,7 +1207,9 @@ class Codec:
                     main.wait_stream(st)
                     syms[k].record_stream(main)
                 with ops.static_schedules(piped and i + 1 < len(order)):
-                    if hd["steps"] is not None:
+                    if mapd[k] is not None:
+                        y_hat = ops.dequant_step_map(syms[k], hypers[k], mapd[k], lut)
+                    elif hd["steps"] is not None:
                         y_hat = ops.dequant_step(syms[k], hypers[k], stepd[k][0])
                     else:
                         y_hat = ops.dequant_split3(syms[k], hypers[k]) if m._synthesis.takes_s3(hd["h"], hd["w"]) else ops.dequant_scale_normal(syms[k], hypers[k])

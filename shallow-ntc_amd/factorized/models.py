@@ -76,8 +76,8 @@ class Model(_ms.Model):
                 ops.check_conv_status()
         return y_hat, None, None, bits
 
-    def decode(self, y_hat, symbols, image_hw, reference=None, check=True, step=None):
-        self._check_step_arguments("decode", step)          # NotImplementedError: quantisation steps are the hyperprior models'
+    def decode(self, y_hat, symbols, image_hw, reference=None, check=True, step=None, step_offsets=None):
+        self._check_step_arguments("decode", step, step_offsets=step_offsets)   # NotImplementedError: quantisation steps are the hyperprior models'
         with torch.cuda.device(self.device):
             recon = self._synthesis(y_hat)
             if reference is None:

@@ -583,15 +583,22 @@ class Model:
                 ops.check_conv_status()
         return z_hat, sym, bits_z, bits_y
 
-    def decode(self, z_hat, symbols, image_hw, reference=None, check=True, step=None):
+    def decode(self, z_hat, symbols, image_hw, reference=None, check=True, step=None, step_offsets=None):
         """(z_hat, symbols) -> hyper-synthesis -> y_hat = symbols + mu -> synthesis -> uint8 pixels
         [n, H, W, 3] (and the per-image integer SSE against ``reference`` if given).  ``check`` as in ``encode``.
         ``step``: the ladder index (or one per image) the symbols were quantised with (``compress(step=...)``):
-        y_hat = fma(step_size(k), symbols, mu)."""
-        self._check_step_arguments("decode", step)
-        steps = None if step is None else self._get_codec()._steps(step, symbols.shape[0])
+        y_hat = fma(step_size(k), symbols, mu).  ``step_offsets``: the per-position offsets they were quantised with
+        (``compress(step_offsets=...)``): k = clip(step + step_offsets) per latent position."""
+        self._check_step_arguments("decode", step, step_offsets=step_offsets)
+        steps, kmap = None, None
+        if step is not None or step_offsets is not None:
+            codec = self._get_codec()
+            steps, kmap = codec._quant(step, step_offsets, symbols.shape[0], int(image_hw[0]), int(image_hw[1]))
         with torch.cuda.device(self.device):
-            if steps is not None:
+            if kmap is not None:
+                mu = self._hyper_synthesis.leading_channels(z_hat, symbols.shape[-1])
+                y_hat = ops.dequant_step_map(symbols, mu, codec._map_tensor(kmap), codec._map_lut())
+            elif steps is not None:
                 mu = self._hyper_synthesis.leading_channels(z_hat, symbols.shape[-1])
                 y_hat = ops.dequant_step(symbols, mu, self._get_codec()._step_tensors(steps)[0])
             elif self._synthesis.takes_s3(symbols.shape[1], symbols.shape[2]):      # bf16x3: y_hat leaves the dequantisation pre-split
@@ -666,7 +673,7 @@ class Model:
             self._codec = Codec(self)
         return self._codec
 
-    def compress(self, x, itinf=None, step=None, target_bpp=None) -> bytes:
+    def compress(self, x, itinf=None, step=None, target_bpp=None, step_offsets=None) -> bytes:
         """Images -> self-contained bitstream (rANS over the integer CDF tables of both entropy models).
         ``itinf`` = dict(steps, seed=0, check_every=None): refine the latents of THESE images by SGA iterative inference first
         (``initialize_itinf`` + ``steps`` x ``itinf_train_step(x, seed=seed, fetch=False)`` under the model's own tau / learning-rate
@@ -693,34 +700,47 @@ class Model:
         those steps, a candidate is eligible only while its bits + the flushed lane states fit the image's budget (where no step
         fits, the candidate with the fewest bits wins), and the steps are NOT chosen again after refinement -- a refined image may
         leave room in its budget that a finer step would have used.  The report then adds quant_step, lam, and with
-        ``target_bpp`` budget_bits, met."""
-        self._check_step_arguments("compress", step, target_bpp, itinf)
+        ``target_bpp`` budget_bits, met.
+        ``step_offsets`` (integers [n, h, w], (h, w) = ``step_offsets_shape(H, W)``, each in [-64, 64]): region-of-interest coding.
+        The ladder index of latent position p of image i is clip(step_i + step_offsets[i, p], STEP_MIN, STEP_MAX), shared by
+        the position's channels, with step_i the image's ``step`` (default 0) or the index ``target_bpp`` chooses (the report
+        then adds map_bits, the 24 bits per run of the map counted in the prediction).  A map that varies inside an image is
+        written as wire format 7; a constant one is the file of ``step=`` those indexes and all zeros the file of
+        ``compress(x)``, byte for byte.  ``entropy_coding.roi_offsets`` makes offsets from a pixel mask.  Excludes ``itinf``."""
+        self._check_step_arguments("compress", step, target_bpp, itinf, step_offsets)
         if itinf is not None:
             return self._compress_itinf(x, **itinf)
-        if step is None and target_bpp is None:
+        if step is None and target_bpp is None and step_offsets is None:
             return self._get_codec().compress(x)
         codec = self._get_codec()
-        blob = codec.compress(x, step=step, target_bpp=target_bpp)
+        blob = codec.compress(x, step=step, target_bpp=target_bpp, step_offsets=step_offsets)
         if target_bpp is not None:
             self.last_compress_report = codec.last_report
         return blob
 
-    def _check_step_arguments(self, where, step, target_bpp=None, itinf=None):
+    def _check_step_arguments(self, where, step, target_bpp=None, itinf=None, step_offsets=None):
         """The refusals of the quantisation-step arguments that need no image: every one before any launch."""
-        if step is None and target_bpp is None:
+        if step is None and target_bpp is None and step_offsets is None:
             return
         if self.factorized:
-            raise NotImplementedError(f"{where}(step / target_bpp): a factorized-prior model's per-channel tables would have to be "
-                                      "rebuilt per step; mean-scale hyperprior models only")
+            raise NotImplementedError(f"{where}(step / target_bpp / step_offsets): a factorized-prior model's per-channel tables "
+                                      "would have to be rebuilt per step; mean-scale hyperprior models only")
         if step is not None and target_bpp is not None:
             raise ValueError(f"{where}: step and target_bpp exclude each other")
         if itinf is not None:
-            raise ValueError(f"{where}: step / target_bpp and itinf exclude each other")
+            raise ValueError(f"{where}: step / target_bpp / step_offsets and itinf exclude each other (SGA on a step map is not "
+                             "implemented)")
         if self._precision != "fp32":
-            raise NotImplementedError(f"{where}(step / target_bpp) runs in precision 'fp32', not {self._precision!r}: the pre-split "
-                                      "dequantisation is not extended")
+            raise NotImplementedError(f"{where}(step / target_bpp / step_offsets) runs in precision 'fp32', not {self._precision!r}: "
+                                      "the pre-split dequantisation is not extended")
 
-    def coded_cost(self, x, latent_rvs=None, step=None, lam=None):
+    def step_offsets_shape(self, H, W):
+        """(h, w) of ``step_offsets`` for H x W images: the resolution of the latents y (``Codec.latent_shapes``)."""
+        if self.factorized:
+            raise NotImplementedError("step_offsets_shape: a factorized-prior model takes no step_offsets; mean-scale hyperprior models only")
+        return tuple(int(v) for v in self._get_codec().latent_shapes(int(H), int(W))[4:])
+
+    def coded_cost(self, x, latent_rvs=None, step=None, lam=None, step_offsets=None):
         """Per image, the cost of what ``decompress`` will output for ``latent_rvs`` (None: the encoder's latents of x) coded at
         ``step`` (None: step 1; a ladder index or one per image as in ``compress``), without
         writing a file: dict of float64 arrays [n] -- ``bits_z`` / ``bits_y`` = ``entropy_coding.rans_cost`` of the symbols the
@@ -728,8 +748,8 @@ class Model:
         rounding slack, DESIGN.md 4.7, are not in it), ``bits`` their sum, ``sse`` the integer SSE of the decoded uint8 pixels,
         ``D`` = the MSE of those pixels on the 0-255 scale (``distortion="ms_ssim"``: 1 - (MS-)SSIM of them, and ``msssim``),
         ``J`` = bits / (H W) + ``lam`` * D with ``lam`` the scheduled rd_lambda (``lam`` given: one weight per image instead, as
-        ``compress(x, itinf=dict(step=...))`` judges its candidates).  One host read-back."""
-        self._check_step_arguments("coded_cost", step)
+        ``compress(x, itinf=dict(step=...))`` judges its candidates).  ``step_offsets``: as in ``compress``.  One host read-back."""
+        self._check_step_arguments("coded_cost", step, step_offsets=step_offsets)
         x = self._as_device_images(x)
         n, h, w, c = x.shape
         ssim = self._distortion == "ms_ssim"
@@ -737,6 +757,9 @@ class Model:
             ops.msssim_scale_sizes(h, w)                              # ValueError before any launch
         codec = self._get_codec()
         kw = {} if step is None else dict(step=codec._steps(step, n))
+        if step_offsets is not None:
+            from ..entropy_coding import check_offsets
+            kw["step_offsets"] = check_offsets(step_offsets, n, *codec.latent_shapes(h, w)[4:])       # ValueError before any launch
         with torch.cuda.device(self.device):
             if latent_rvs is None:
                 latent_rvs = self.infer_latent_rvs(x)

@@ -1297,6 +1297,42 @@ def dequant_step(symbols, hyper, step):
     return y_hat
 
 
+def _check_step_map(a, kmap, lut, where):
+    """``kmap`` int8 [n, h, w] = one ladder index per latent position of ``a`` [n, h, w, c]; ``lut`` = entropy_coding.step_lut:
+    float32 [2, 65], the steps and inverse steps of the ladder."""
+    if not (isinstance(kmap, torch.Tensor) and kmap.dtype == torch.int8 and tuple(kmap.shape) == tuple(a.shape[:3])
+            and kmap.is_contiguous() and kmap.device == a.device):
+        raise ValueError(f"{where}: kmap int8 {tuple(a.shape[:3])} on the latents' device, one ladder index per position")
+    if not (isinstance(lut, torch.Tensor) and lut.dtype == torch.float32 and tuple(lut.shape) == (2, 65) and lut.is_contiguous()
+            and lut.device == a.device):
+        raise ValueError(f"{where}: lut float32 [2, 65] (entropy_coding.step_lut)")
+
+
+def step_map_symbols(y, hyper, base_ids, kmap, lut):
+    """``step_symbols`` with one ladder index per latent POSITION (csrc/quant_step_map.hip): at index k = kmap[image, position]
+    symbols = rint((y - mu) * lut[1, k + 32]), table ids = clamp(base_ids - k, 0, 63) for all c channels of the position."""
+    n, hw, c, stride = _check_step_inputs(y, hyper, ())
+    _check_step_map(y, kmap, lut, "step_map_symbols")
+    if base_ids.dtype != torch.int16 or tuple(base_ids.shape) != tuple(y.shape) or not base_ids.is_contiguous():
+        raise ValueError("step_map_symbols: base_ids int16 (uint16 storage) like y")
+    sym = torch.empty(y.shape, dtype=torch.int32, device=y.device)
+    tid = torch.empty_like(base_ids)
+    capi.call("sntc_step_map_symbols", _ptr(y), _ptr(hyper), n, hw, c, stride, _ptr(base_ids), _ptr(kmap), _ptr(lut), _ptr(sym),
+              _ptr(tid), _stream())
+    return sym, tid
+
+
+def dequant_step_map(symbols, hyper, kmap, lut):
+    """y_hat = fma(lut[0, k + 32], symbols, mu) at k = kmap[image, position]: ``dequant_step`` with one index per position."""
+    n, hw, c, stride = _check_step_inputs(symbols, hyper, ())
+    _check_step_map(symbols, kmap, lut, "dequant_step_map")
+    if symbols.dtype != torch.int32:
+        raise ValueError("dequant_step_map: symbols int32")
+    y_hat = torch.empty(symbols.shape, dtype=torch.float32, device=symbols.device)
+    capi.call("sntc_dequant_step_map", _ptr(symbols), _ptr(hyper), n, hw, c, stride, _ptr(kmap), _ptr(lut), _ptr(y_hat), _stream())
+    return y_hat
+
+
 # ------------------------------------------------------------------------------------------
 # SGA iterative inference (include/sntc.h "SGA" section)
 # ------------------------------------------------------------------------------------------
