@@ -422,6 +422,12 @@ int sntc_concat_channels(const float* a, int ca, const float* b, int cb, int64_t
  * pixels_out (the decoder's last step); sse_out is then ignored. */
 int sntc_pixels_sse(const float* x, const float* x_hat, int n, int h, int w, int c, int hs, int ws,
                     uint8_t* pixels_out, unsigned long long* sse_out, void* stream);
+/* The integer squared error of decoded uint8 pixels [n,h,w,c] against x [n,h,w,c] quantised the same way (the rule of
+ * sntc_pixels_sse; common/data_lib.py:48-52, common/image_utils.py:22-23) over every block x block pixel block: out uint32
+ * [n][ceil(h / block)][ceil(w / block)], OVERWRITTEN; blocks at the right and bottom edges may be ragged.  Integers end to end
+ * (one wave per block, one store per block): exact, and the per-image sums are sntc_pixels_sse's.  block^2 c 255^2 must stay
+ * below 2^32 (SNTC_ERR_BAD_SHAPE otherwise). */
+int sntc_block_sse(const float* x, const uint8_t* pixels, int n, int h, int w, int c, int block, uint32_t* out, void* stream);
 /* Training-mode distortion (SGA): sum over (255*(x - x_hat))^2 in float, per image, double out. */
 int sntc_float_sse(const float* x, const float* x_hat, int n, int h, int w, int c, int hs, int ws,
                    double* sse_out, void* stream);
@@ -676,6 +682,25 @@ int sntc_sga_normal_step_fwd(const float* y_loc, const float* hyper, int n, int6
 int sntc_sga_normal_step_bwd(const float* g_ytilde, const float* sprime, const float* dbits_dv, const float* dbits_draw,
                              float weight, int n, int64_t hw, int c, const float* quant_step, const float* inv_step,
                              const float* dweight, float* g_yloc, float* g_hyper, void* stream);
+/* sntc_sga_normal_step_fwd with one ladder index per latent POSITION (mshyper/models.py:285-291 and
+ * common/latent_rvs_utils.py:8-48 on a grid that varies inside the image; region-of-interest coding, the step rule of
+ * sntc_step_map_symbols / sntc_dequant_step_map above): kmap int8 [n][hw] on the device, one index for the c channels of a
+ * position, clamped to [-32, 32] before it is used; lut float [2][65] = [step | inv_step] by index + 32 (the table of
+ * sntc_step_map_symbols).  At k = kmap[image][position]: u = (y_loc - mu) * lut[1][k + 32], y~ = fmaf(lut[0][k + 32], v, mu), the
+ * rate under the table k places down the ladder.  With a map constant per image the four element-wise outputs are
+ * sntc_sga_normal_step_fwd's at that index, bit for bit; where u is an integer y~ is sntc_dequant_step_map's value of
+ * sntc_step_map_symbols' symbol.  Same Gumbel keys, same 16-byte / element-wise paths.  n <= 65535. */
+int sntc_sga_normal_step_map_fwd(const float* y_loc, const float* hyper, int n, int64_t hw, int c, float tau, const float* noise,
+                                 uint64_t seed, uint64_t step, const int8_t* kmap, const float* lut, float* y_tilde, float* sprime,
+                                 float* dbits_dv, float* dbits_draw, double* bits, void* stream);
+/* Its backward half (mshyper/models.py:285-291, common/latent_rvs_utils.py:8-48): with step / inv_step of the position's index,
+ * a = sprime inv_step, dv = weight dbits_dv, g = g_ytilde,
+ *   g_yloc = (g step + dv) a;  g_hyper = [g (1 - step a) - dv a | weight dbits_draw]
+ * -- sntc_sga_normal_step_bwd at dweight = 1.0f: on a map the distortion's weight sits on the pixels
+ * (sntc_distortion_grad_weighted), not here. */
+int sntc_sga_normal_step_map_bwd(const float* g_ytilde, const float* sprime, const float* dbits_dv, const float* dbits_draw,
+                                 float weight, int n, int64_t hw, int c, const int8_t* kmap, const float* lut, float* g_yloc,
+                                 float* g_hyper, void* stream);
 /* UQLatentRV.sample(training, method, offset, **kwargs) / .quantize(offset) (common/latent_rvs_lib.py:77-116) on [npix, c]
  * values: u = loc - offset (offset NULL = none; else element (p, ch) is offset[p * offset_stride + ch], e.g. the mean half of
  * the hyper-synthesis output with offset_stride = 2 c; offset_stride 0 broadcasts a per-channel [c] offset).  mode 0: round-half-even(u) + offset (training=False, :95-102; also
@@ -692,6 +717,15 @@ int sntc_sga_chain(const float* g, const float* dbits, const float* sprime, floa
  * un-padded h x w region; g_xhat[n,hs,ws,c] = scale (x_hat - x), zero in the padded margin. */
 int sntc_distortion_grad(const float* x, const float* x_hat, int n, int h, int w, int c, int hs, int ws, float scale,
                          float* g_xhat, double* sse, void* stream);
+/* sntc_distortion_grad with a weight per block x block pixels (common/data_lib.py:48-52; the distortion of SGA on a step map,
+ * where the weight varies inside an image and so cannot be applied after the synthesis adjoint): weights float [n][hb][wb] on
+ * the device, hb block >= hs and wb block >= ws; pixel (r, s) takes omega = weights[image][r / block][s / block].
+ *   g_xhat = (scale omega) (x_hat - x) in the h x w region, zero in the margin;
+ *   sse[n] = the UNWEIGHTED sum of (255 (x - x_hat))^2, as sntc_distortion_grad leaves it;  wsse[n] = sum omega (255 (x - x_hat))^2.
+ * Both sums are doubles, OVERWRITTEN.  With every weight 1.0f: g_xhat and sse are sntc_distortion_grad's, bit for bit. */
+int sntc_distortion_grad_weighted(const float* x, const float* x_hat, int n, int h, int w, int c, int hs, int ws, float scale,
+                                  const float* weights, int hb, int wb, int block, float* g_xhat, double* sse, double* wsse,
+                                  void* stream);
 /* Backward of the activation + residual split of sntc_two_layer_tail: t is the forward input, g_h the gradient
  * w.r.t. h; g_t[npix, cp] = [d act(base) | g_h (if has_res) | zeros up to cp]. */
 /* Input gradient of the tail's output layer (Conv2DTranspose 5x5 / 2, ch -> 3, SAME; w2 [5,5,3,ch]):

@@ -121,6 +121,36 @@ __global__ void __launch_bounds__(256) pixels_sse_vec4_kernel(const float* __res
   if (threadIdx.x == 0) atomicAdd(sse + img, part[0] + part[1] + part[2] + part[3]);
 }
 
+// The integer squared error of the decoder's uint8 pixels against to_pixel(x) per block x block pixel block (the
+// weighted cost of a step map, and the project's ROI metric).  One wave per block, a workgroup = 4 blocks: the lanes stride over
+// the block's rows (ragged at the right and bottom edges: rows / cols are cut at h / w), the sum is a 32-bit integer from the
+// lane to the one plain store of lane 0 -- exact, no atomics, independent of the launch geometry.  The host checks that
+// block^2 c 255^2 fits 32 bits.
+__global__ void __launch_bounds__(256) block_sse_kernel(const float* __restrict__ x, const uint8_t* __restrict__ px, int h, int w,
+                                                        int c, int block, int hb, int wb, long long nblocks,
+                                                        unsigned* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const long long id = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);      // wave-uniform: the whole wave leaves together
+  if (id >= nblocks) return;
+  const int bx = (int)(id % wb);
+  const long long t = id / wb;
+  const int by = (int)(t % hb);
+  const long long img = t / hb;
+  const int r0 = by * block, c0 = bx * block;
+  const int rows = min(block, h - r0), cols = min(block, w - c0);          // >= 1: hb = ceil(h / block), wb = ceil(w / block)
+  const int rowlen = cols * c, total = rows * rowlen;
+  unsigned acc = 0u;
+  for (int e = lane; e < total; e += 64) {
+    const int rr = e / rowlen, o = e - rr * rowlen;
+    const long long at = ((img * h + r0 + rr) * w + c0) * c + o;
+    const int d = to_pixel(x[at]) - (int)px[at];
+    acc += (unsigned)(d * d);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if (lane == 0) out[id] = acc;
+}
+
 __global__ void __launch_bounds__(256) float_sse_kernel(const float* __restrict__ x, const float* __restrict__ xh, int h, int w,
                                                         int c, int hs, int ws, double* __restrict__ sse) {
   const int img = blockIdx.y;
@@ -435,6 +465,22 @@ extern "C" int sntc_pixels_sse(const float* x, const float* x_hat, int n, int h,
   const int cap1 = x ? std::max(16, std::min(256, 2048 / n)) : 512;
   if (b > cap1) b = cap1;
   hipLaunchKernelGGL(pixels_sse_kernel, dim3(b, n), dim3(256), 0, s, x, x_hat, h, w, c, hs, ws, pixels_out, sse_out);
+  SNTC_HIP(hipGetLastError());
+  return SNTC_OK;
+}
+
+extern "C" int sntc_block_sse(const float* x, const uint8_t* pixels, int n, int h, int w, int c, int block, uint32_t* out,
+                             void* stream) {
+  if (!x || !pixels || !out) return fail(SNTC_ERR_BAD_SHAPE, "sntc_block_sse: null argument");
+  if (n < 1 || h < 1 || w < 1 || c < 1 || block < 1) return fail(SNTC_ERR_BAD_SHAPE, "sntc_block_sse: bad sizes");
+  const int64_t unit = (int64_t)c * 255 * 255, top = (1LL << 32) - 1;       // the largest error of one pixel; of one sum
+  if (unit > top || block > 65535 || (int64_t)block * block > top / unit)
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_block_sse: block^2 c 255^2 must stay below 2^32 (the sums are 32-bit integers)");
+  const int hb = (h + block - 1) / block, wb = (w + block - 1) / block;
+  const int64_t nblocks = (int64_t)n * hb * wb;
+  if ((nblocks + 3) / 4 > 0x7fffffffLL) return fail(SNTC_ERR_BAD_SHAPE, "sntc_block_sse: too many blocks for one launch");
+  hipLaunchKernelGGL(block_sse_kernel, dim3((unsigned)((nblocks + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, pixels, h, w, c, block,
+                     hb, wb, (long long)nblocks, out);
   SNTC_HIP(hipGetLastError());
   return SNTC_OK;
 }

@@ -20,14 +20,11 @@
 
 namespace sntc {
 
-constexpr int kMapMin = -32, kMapMax = 32;                  // ladder indexes a map may hold
-constexpr int kMapLut = kMapMax - kMapMin + 1;              // entries of a row of the step table: [step | inv_step]
+// kMapMin / kMapMax / kMapLut and map_index: step_rules.h (the SGA map kernels of sga.hip read the same table)
 constexpr int kMapLadderMax = 16;                           // candidate bases of one ladder launch (their sums live in registers)
 constexpr int kMapLadderThreads = 1024;
 constexpr int kMapLadderGrid = 512;                         // workgroups of a launch, about
 constexpr int kMapLadderLdsLimit = kRansLdsTotal;           // descriptors + cost_q staged in LDS up to here
-
-__device__ __forceinline__ int map_index(int k) { return min(max(k, kMapMin), kMapMax); }
 
 typedef int sm_i32x4 __attribute__((ext_vector_type(4)));
 typedef float sm_f32x4 __attribute__((ext_vector_type(4)));

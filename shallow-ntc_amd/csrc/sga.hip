@@ -147,21 +147,34 @@ __global__ void __launch_bounds__(256) sga_normal_bwd_kernel(const float* __rest
 // sga_normal_fwd_kernel: (seed, step, element index in the batch).
 // Layout of step_symbols_kernel (quant_step.hip): grid (blocks per image, n); a thread's unit is V consecutive channels of a
 // pixel (V = 4: 16-byte loads and stores, c % 4 == 0 and aligned pointers; V = 1 otherwise).
-template <int V>
+// MAP ("SGA on a step map"; the same reference lines, mshyper/models.py:285-291 and
+// common/latent_rvs_utils.py:8-48, with the grid varying per latent position): the triple comes from where the coder's map
+// kernels take it (quant_step_map.hip) -- a unit is V channels of ONE position, so the thread reads one byte of kmap [n][hw],
+// clamps it (map_index) and reads step and inverse step from lut [2][kMapLut]; k is then a per-lane value and nothing is
+// recomputed with expf.  One body for both: the per-image instances read their triple once, before the loop, as before.
+template <int V, bool MAP>
 __global__ void __launch_bounds__(256) sga_normal_step_fwd_kernel(const float* __restrict__ y_loc, const float* __restrict__ hyper,
                                                                   long long hw, int c, float tau, const float* __restrict__ noise,
                                                                   unsigned long long seed, unsigned long long step,
                                                                   const float* __restrict__ qstep, const float* __restrict__ inv_step,
-                                                                  const int* __restrict__ shift, float* __restrict__ y_tilde,
+                                                                  const int* __restrict__ shift, const signed char* __restrict__ kmap,
+                                                                  const float* __restrict__ lut, float* __restrict__ y_tilde,
                                                                   float* __restrict__ sprime, float* __restrict__ dbits_dv,
                                                                   float* __restrict__ dbits_draw, double* __restrict__ bits) {
   const int img = blockIdx.y, cu = c / V;                    // units per pixel
-  const float st = qstep[img], inv = inv_step[img], k = (float)shift[img];
+  float st = 1.0f, inv = 1.0f, k = 0.0f;
+  if constexpr (!MAP) { st = qstep[img]; inv = inv_step[img]; k = (float)shift[img]; }
   const long long nunit = hw * cu, base = (long long)img * hw * c;
   double acc = 0.0;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nunit; i += (long long)gridDim.x * blockDim.x) {
     const long long p = i / cu;
     const int ch = (int)(i - p * cu) * V;
+    if constexpr (MAP) {
+      const int ki = map_index(kmap[(long long)img * hw + p]);
+      st = lut[ki - kMapMin];
+      inv = lut[kMapLut + ki - kMapMin];
+      k = (float)ki;
+    }
     const long long gi = base + i * V;                       // first element of the unit, index in the batch
     const float* hp = hyper + ((long long)img * hw + p) * 2 * c + ch;
     float y[V], mu[V], raw[V], g[2 * V], yt[V], sp[V], dv[V], dr[V];
@@ -211,18 +224,27 @@ __global__ void __launch_bounds__(256) sga_normal_step_fwd_kernel(const float* _
 // With a = s' inv_step, dv = w dbits_dv, g = g_yt dweight[image] (the image's lambda over the launch's):
 //   g_yloc = (g step + dv) a;   g_mu = g (1 - step a) - dv a;   g_raw = w dbits_draw
 // -- at step = inv_step = dweight = 1 every operation is sga_normal_bwd_kernel's.
-template <int V>
+// MAP: step and inverse step per position from (kmap, lut) as in the forward kernel, and no dweight (g = g_yt): on a map the
+// weight sits on the pixels, inside the distortion (distortion_grad_weighted_kernel below).
+template <int V, bool MAP>
 __global__ void __launch_bounds__(256) sga_normal_step_bwd_kernel(const float* __restrict__ g_yt, const float* __restrict__ sprime,
                                                                   const float* __restrict__ dbits_dv, const float* __restrict__ dbits_draw,
                                                                   float w, long long hw, int c, const float* __restrict__ qstep,
                                                                   const float* __restrict__ inv_step, const float* __restrict__ dweight,
+                                                                  const signed char* __restrict__ kmap, const float* __restrict__ lut,
                                                                   float* __restrict__ g_yloc, float* __restrict__ g_hyper) {
   const int img = blockIdx.y, cu = c / V;
-  const float st = qstep[img], inv = inv_step[img], dw = dweight[img];
+  float st = 1.0f, inv = 1.0f, dw = 1.0f;
+  if constexpr (!MAP) { st = qstep[img]; inv = inv_step[img]; dw = dweight[img]; }
   const long long nunit = hw * cu, base = (long long)img * hw * c;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nunit; i += (long long)gridDim.x * blockDim.x) {
     const long long p = i / cu;
     const int ch = (int)(i - p * cu) * V;
+    if constexpr (MAP) {
+      const int ki = map_index(kmap[(long long)img * hw + p]);
+      st = lut[ki - kMapMin];
+      inv = lut[kMapLut + ki - kMapMin];
+    }
     const long long gi = base + i * V;
     float* hp = g_hyper + ((long long)img * hw + p) * 2 * c + ch;
     float gt[V], sp[V], bv[V], br[V], gy[V], gm[V], gr[V];
@@ -241,7 +263,7 @@ __global__ void __launch_bounds__(256) sga_normal_step_bwd_kernel(const float* _
     }
 #pragma unroll
     for (int e = 0; e < V; ++e) {
-      const float g = gt[e] * dw, a = sp[e] * inv, dv = w * bv[e];
+      const float g = MAP ? gt[e] : gt[e] * dw, a = sp[e] * inv, dv = w * bv[e];
       gy[e] = (g * st + dv) * a;
       gm[e] = g * (1.0f - st * a) - dv * a;
       gr[e] = w * br[e];
@@ -408,6 +430,55 @@ __global__ void __launch_bounds__(256) distortion_grad_kernel(const float* __res
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(sse + img, part[0] + part[1] + part[2] + part[3]);
+}
+
+// ---- the same with a weight per block x block pixels (the distortion of SGA on a step map) ----
+// g = (scale omega) (x_hat - x), omega = weights[img][r / block][col / block]; sse[n] stays the UNWEIGHTED sum (the step's mse /
+// psnr keep their meaning), wsse[n] = sum omega (255 d)^2.  Both sums are doubles, reduced as distortion_grad_kernel reduces.
+// The weight indexes are checked against (hb, wb) although the host already refuses hb block < hs: a thread whose pixel had no
+// weight would store 0 and add nothing.
+__global__ void __launch_bounds__(256) distortion_grad_weighted_kernel(const float* __restrict__ x, const float* __restrict__ xh,
+                                                                       int h, int w, int c, int hs, int ws, float scale,
+                                                                       const float* __restrict__ weights, int hb, int wb, int block,
+                                                                       float* __restrict__ g, double* __restrict__ sse,
+                                                                       double* __restrict__ wsse) {
+  const int img = blockIdx.y;
+  const int64_t per_s = (int64_t)hs * ws * c;
+  const int rowlen_s = ws * c;
+  double acc = 0, wacc = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per_s; i += (int64_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / rowlen_s);
+    const int o = (int)(i - (int64_t)r * rowlen_s);
+    float gv = 0.0f;
+    if (r < h && o < w * c) {
+      const int rb = r / block, cb = (o / c) / block;
+      if (rb < hb && cb < wb) {
+        const float om = weights[((int64_t)img * hb + rb) * wb + cb];
+        const float d = xh[img * per_s + i] - x[((int64_t)img * h + r) * w * c + o];
+        gv = (scale * om) * d;
+        const float d255 = 255.0f * d;
+        const float sq = d255 * d255;
+        acc += (double)sq;
+        wacc += (double)om * (double)sq;
+      }
+    }
+    g[img * per_s + i] = gv;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    acc += __shfl_down(acc, o, 64);
+    wacc += __shfl_down(wacc, o, 64);
+  }
+  __shared__ double part[4], wpart[4];
+  if ((threadIdx.x & 63) == 0) {
+    part[threadIdx.x >> 6] = acc;
+    wpart[threadIdx.x >> 6] = wacc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicAdd(sse + img, part[0] + part[1] + part[2] + part[3]);
+    atomicAdd(wsse + img, wpart[0] + wpart[1] + wpart[2] + wpart[3]);
+  }
 }
 
 // ---- two-layer tail backward: g_t[..., :CH] = d act(base) (g_h), g_t[..., CH:2CH] = g_h (residual), zero padding to CP ----
@@ -790,6 +861,12 @@ static unsigned step_grid(int64_t nunit) {
   return (unsigned)std::max<int64_t>((need + passes - 1) / passes, 1);
 }
 
+// the arguments an instance of the shared step kernels never reads: the per-image ones take no map, the map ones no triple
+static const signed char* const kNoMap = nullptr;
+static const float* const kNoLut = nullptr;
+static const float* const kNoStep = nullptr;
+static const int* const kNoShift = nullptr;
+
 extern "C" int sntc_sga_normal_step_fwd(const float* y_loc, const float* hyper, int n, int64_t hw, int c, float tau,
                                         const float* noise, uint64_t seed, uint64_t step, const float* quant_step,
                                         const float* inv_step, const int32_t* shift, float* y_tilde, float* sprime,
@@ -804,13 +881,13 @@ extern "C" int sntc_sga_normal_step_fwd(const float* y_loc, const float* hyper, 
                    aligned16(sprime) && aligned16(dbits_dv) && aligned16(dbits_draw);
   const int* sh = reinterpret_cast<const int*>(shift);
   if (vec)
-    hipLaunchKernelGGL((sga_normal_step_fwd_kernel<4>), dim3(step_grid(hw * (c / 4)), n), dim3(256), 0, s, y_loc, hyper, (long long)hw, c,
-                       tau, noise, (unsigned long long)seed, (unsigned long long)step, quant_step, inv_step, sh, y_tilde, sprime,
-                       dbits_dv, dbits_draw, bits);
+    hipLaunchKernelGGL((sga_normal_step_fwd_kernel<4, false>), dim3(step_grid(hw * (c / 4)), n), dim3(256), 0, s, y_loc, hyper,
+                       (long long)hw, c, tau, noise, (unsigned long long)seed, (unsigned long long)step, quant_step, inv_step, sh,
+                       kNoMap, kNoLut, y_tilde, sprime, dbits_dv, dbits_draw, bits);
   else
-    hipLaunchKernelGGL((sga_normal_step_fwd_kernel<1>), dim3(step_grid(hw * c), n), dim3(256), 0, s, y_loc, hyper, (long long)hw, c,
-                       tau, noise, (unsigned long long)seed, (unsigned long long)step, quant_step, inv_step, sh, y_tilde, sprime,
-                       dbits_dv, dbits_draw, bits);
+    hipLaunchKernelGGL((sga_normal_step_fwd_kernel<1, false>), dim3(step_grid(hw * c), n), dim3(256), 0, s, y_loc, hyper,
+                       (long long)hw, c, tau, noise, (unsigned long long)seed, (unsigned long long)step, quant_step, inv_step, sh,
+                       kNoMap, kNoLut, y_tilde, sprime, dbits_dv, dbits_draw, bits);
   SNTC_HIP(hipGetLastError());
   return SNTC_OK;
 }
@@ -825,11 +902,60 @@ extern "C" int sntc_sga_normal_step_bwd(const float* g_ytilde, const float* spri
   const bool vec = c % 4 == 0 && aligned16(g_ytilde) && aligned16(sprime) && aligned16(dbits_dv) && aligned16(dbits_draw) &&
                    aligned16(g_yloc) && aligned16(g_hyper);
   if (vec)
-    hipLaunchKernelGGL((sga_normal_step_bwd_kernel<4>), dim3(step_grid(hw * (c / 4)), n), dim3(256), 0, s, g_ytilde, sprime, dbits_dv,
-                       dbits_draw, weight, (long long)hw, c, quant_step, inv_step, dweight, g_yloc, g_hyper);
+    hipLaunchKernelGGL((sga_normal_step_bwd_kernel<4, false>), dim3(step_grid(hw * (c / 4)), n), dim3(256), 0, s, g_ytilde, sprime,
+                       dbits_dv, dbits_draw, weight, (long long)hw, c, quant_step, inv_step, dweight, kNoMap, kNoLut, g_yloc, g_hyper);
   else
-    hipLaunchKernelGGL((sga_normal_step_bwd_kernel<1>), dim3(step_grid(hw * c), n), dim3(256), 0, s, g_ytilde, sprime, dbits_dv,
-                       dbits_draw, weight, (long long)hw, c, quant_step, inv_step, dweight, g_yloc, g_hyper);
+    hipLaunchKernelGGL((sga_normal_step_bwd_kernel<1, false>), dim3(step_grid(hw * c), n), dim3(256), 0, s, g_ytilde, sprime,
+                       dbits_dv, dbits_draw, weight, (long long)hw, c, quant_step, inv_step, dweight, kNoMap, kNoLut, g_yloc, g_hyper);
+  SNTC_HIP(hipGetLastError());
+  return SNTC_OK;
+}
+
+// The same pair with the triple per latent position: kmap int8 [n][hw] (any byte: clamped to the ladder in the kernel), lut the
+// float [2][65] step table of the coder's map kernels.  Same grid, same V = 4 / V = 1 rule, same Gumbel keys.
+extern "C" int sntc_sga_normal_step_map_fwd(const float* y_loc, const float* hyper, int n, int64_t hw, int c, float tau,
+                                            const float* noise, uint64_t seed, uint64_t step, const int8_t* kmap, const float* lut,
+                                            float* y_tilde, float* sprime, float* dbits_dv, float* dbits_draw, double* bits,
+                                            void* stream) {
+  if (!y_loc || !hyper || !kmap || !lut || !y_tilde || !sprime || !dbits_dv || !dbits_draw || !bits)
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_sga_normal_step_map_fwd: null argument");
+  if (n < 1 || n > 65535 || hw < 1 || c < 1 || !(tau > 0.0f))
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_sga_normal_step_map_fwd: bad sizes / tau (1 <= n <= 65535)");
+  if (reinterpret_cast<uintptr_t>(lut) % 4 != 0) return fail(SNTC_ERR_BAD_SHAPE, "sntc_sga_normal_step_map_fwd: misaligned lut");
+  hipStream_t s = (hipStream_t)stream;
+  if (int zrc = zero_async(bits, sizeof(double) * n, s)) return zrc;
+  const bool vec = c % 4 == 0 && aligned16(y_loc) && aligned16(hyper) && (!noise || aligned16(noise)) && aligned16(y_tilde) &&
+                   aligned16(sprime) && aligned16(dbits_dv) && aligned16(dbits_draw);
+  const signed char* km = reinterpret_cast<const signed char*>(kmap);
+  if (vec)
+    hipLaunchKernelGGL((sga_normal_step_fwd_kernel<4, true>), dim3(step_grid(hw * (c / 4)), n), dim3(256), 0, s, y_loc, hyper,
+                       (long long)hw, c, tau, noise, (unsigned long long)seed, (unsigned long long)step, kNoStep, kNoStep, kNoShift,
+                       km, lut, y_tilde, sprime, dbits_dv, dbits_draw, bits);
+  else
+    hipLaunchKernelGGL((sga_normal_step_fwd_kernel<1, true>), dim3(step_grid(hw * c), n), dim3(256), 0, s, y_loc, hyper,
+                       (long long)hw, c, tau, noise, (unsigned long long)seed, (unsigned long long)step, kNoStep, kNoStep, kNoShift,
+                       km, lut, y_tilde, sprime, dbits_dv, dbits_draw, bits);
+  SNTC_HIP(hipGetLastError());
+  return SNTC_OK;
+}
+
+extern "C" int sntc_sga_normal_step_map_bwd(const float* g_ytilde, const float* sprime, const float* dbits_dv, const float* dbits_draw,
+                                            float weight, int n, int64_t hw, int c, const int8_t* kmap, const float* lut,
+                                            float* g_yloc, float* g_hyper, void* stream) {
+  if (!g_ytilde || !sprime || !dbits_dv || !dbits_draw || !kmap || !lut || !g_yloc || !g_hyper)
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_sga_normal_step_map_bwd: null argument");
+  if (n < 1 || n > 65535 || hw < 1 || c < 1) return fail(SNTC_ERR_BAD_SHAPE, "sntc_sga_normal_step_map_bwd: bad sizes (1 <= n <= 65535)");
+  if (reinterpret_cast<uintptr_t>(lut) % 4 != 0) return fail(SNTC_ERR_BAD_SHAPE, "sntc_sga_normal_step_map_bwd: misaligned lut");
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = c % 4 == 0 && aligned16(g_ytilde) && aligned16(sprime) && aligned16(dbits_dv) && aligned16(dbits_draw) &&
+                   aligned16(g_yloc) && aligned16(g_hyper);
+  const signed char* km = reinterpret_cast<const signed char*>(kmap);
+  if (vec)
+    hipLaunchKernelGGL((sga_normal_step_bwd_kernel<4, true>), dim3(step_grid(hw * (c / 4)), n), dim3(256), 0, s, g_ytilde, sprime,
+                       dbits_dv, dbits_draw, weight, (long long)hw, c, kNoStep, kNoStep, kNoStep, km, lut, g_yloc, g_hyper);
+  else
+    hipLaunchKernelGGL((sga_normal_step_bwd_kernel<1, true>), dim3(step_grid(hw * c), n), dim3(256), 0, s, g_ytilde, sprime,
+                       dbits_dv, dbits_draw, weight, (long long)hw, c, kNoStep, kNoStep, kNoStep, km, lut, g_yloc, g_hyper);
   SNTC_HIP(hipGetLastError());
   return SNTC_OK;
 }
@@ -881,6 +1007,24 @@ extern "C" int sntc_distortion_grad(const float* x, const float* x_hat, int n, i
   int b = grid_for((int64_t)hs * ws * c);
   if (b > 512) b = 512;
   hipLaunchKernelGGL(distortion_grad_kernel, dim3(b, n), dim3(256), 0, s, x, x_hat, h, w, c, hs, ws, scale, g_xhat, sse);
+  SNTC_HIP(hipGetLastError());
+  return SNTC_OK;
+}
+
+extern "C" int sntc_distortion_grad_weighted(const float* x, const float* x_hat, int n, int h, int w, int c, int hs, int ws,
+                                            float scale, const float* weights, int hb, int wb, int block, float* g_xhat,
+                                            double* sse, double* wsse, void* stream) {
+  if (!x || !x_hat || !weights || !g_xhat || !sse || !wsse) return fail(SNTC_ERR_BAD_SHAPE, "sntc_distortion_grad_weighted: null argument");
+  if (n < 1 || n > 65535 || h < 1 || w < 1 || c < 1 || hs < h || ws < w) return fail(SNTC_ERR_BAD_SHAPE, "sntc_distortion_grad_weighted: bad sizes");
+  if (hb < 1 || wb < 1 || block < 1 || (int64_t)hb * block < hs || (int64_t)wb * block < ws)
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_distortion_grad_weighted: the weights must cover the reconstruction (hb block >= hs, wb block >= ws)");
+  hipStream_t s = (hipStream_t)stream;
+  if (int zrc = zero_async(sse, sizeof(double) * n, s)) return zrc;
+  if (int zrc = zero_async(wsse, sizeof(double) * n, s)) return zrc;
+  int b = grid_for((int64_t)hs * ws * c);
+  if (b > 512) b = 512;
+  hipLaunchKernelGGL(distortion_grad_weighted_kernel, dim3(b, n), dim3(256), 0, s, x, x_hat, h, w, c, hs, ws, scale, weights, hb, wb,
+                     block, g_xhat, sse, wsse);
   SNTC_HIP(hipGetLastError());
   return SNTC_OK;
 }

@@ -29,4 +29,12 @@ __device__ __forceinline__ float step_scaled(float d, float inv_step) { return d
 
 __device__ __forceinline__ float step_value_at(float v, float mu, float step) { return fmaf(step, v, mu); }
 
+// A ladder index per latent POSITION (quant_step_map.hip, the SGA map kernels of sga.hip): the host uploads one table `lut`,
+// float32 [2][kMapLut], row 0 = step, row 1 = inv_step, column k - kMapMin; every kernel clamps the byte it reads from a map
+// with map_index before it indexes the table, so a stray byte can never read outside it.
+constexpr int kMapMin = -32, kMapMax = 32;                  // ladder indexes a map may hold
+constexpr int kMapLut = kMapMax - kMapMin + 1;              // entries of a row of the step table: [step | inv_step]
+
+__device__ __forceinline__ int map_index(int k) { return min(max(k, kMapMin), kMapMax); }
+
 }  // namespace sntc

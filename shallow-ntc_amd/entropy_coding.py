@@ -154,6 +154,20 @@ def index_map(steps, offsets):
     return np.clip(base + offsets.astype(np.int64), STEP_MIN, STEP_MAX).astype(np.int8)
 
 
+def position_weights(kmap):
+    """The weight of every latent position's pixels in the distortion of SGA on a step map, a pure function: absolute ladder
+    indexes K int8 [n, h, w] (``index_map``) -> float64 [n, h, w], omega = 1 / step_size(K)^2 -- what ``step_lambdas(1.0, [k])``
+    gives an image whose every position is k (the same modelling choice).  The device copy is this rounded once
+    to float32."""
+    K = np.asarray(kmap)
+    if K.dtype != np.int8 or K.ndim != 3:
+        raise ValueError("position_weights: absolute ladder indexes, int8 [n, h, w]")
+    if K.size and not (STEP_MIN <= int(K.min()) and int(K.max()) <= STEP_MAX):
+        raise ValueError(f"ladder index outside [{STEP_MIN}, {STEP_MAX}]")
+    table = np.array([1.0 / step_size(k) ** 2 for k in range(STEP_MIN, STEP_MAX + 1)], np.float64)
+    return table[K.astype(np.int64) - STEP_MIN]
+
+
 def uniform_steps(kmap):
     """The per-image ladder indexes of a map whose every image is constant (the file is then v5 / v3), else None."""
     flat = kmap.reshape(kmap.shape[0], -1)

@@ -72,6 +72,21 @@ def candidate_wins(j_cand, bits_cand, j_best, bits_best, budget_bits=None, flush
     return np.where(np.asarray(met, bool), eligible & (j_cand < j_best), bits_cand < bits_best)
 
 
+def weighted_distortion(sse_blocks, weights, elements):
+    """D_w of ``coded_cost(..., weighted=True)``, a pure function: ``sse_blocks`` [n, hb, wb] = the integer squared error of the
+    decoded pixels per pixel block (``ops.block_sse``), ``weights`` float64 [n, h, w] = ``entropy_coding.position_weights`` of the
+    map with h >= hb, w >= wb (positions that lie wholly in the padding have no pixels), ``elements`` = H W C.
+    -> float64 [n], sum_p weights[i, p] sse_blocks[i, p] / elements, each image's sum formed exactly (math.fsum) from its
+    rounded products.  With a constant map this is step_lambdas(1.0, [k])[0] * sse_i / elements: the per-image rule's D_i
+    times its weight."""
+    s = np.asarray(sse_blocks, np.float64)
+    w = np.asarray(weights, np.float64)
+    if s.ndim != 3 or w.ndim != 3 or w.shape[0] != s.shape[0] or w.shape[1] < s.shape[1] or w.shape[2] < s.shape[2]:
+        raise ValueError(f"weighted_distortion: blocks {s.shape} against weights {w.shape}")
+    prod = w[:, :s.shape[1], :s.shape[2]] * s
+    return np.array([math.fsum(row.ravel().tolist()) for row in prod], np.float64) / float(elements)
+
+
 def deep_factorized_shapes(channels, num_filters=(3, 3)):
     filters = (1,) + tuple(num_filters) + (1,)
     d = OrderedDict()
@@ -419,10 +434,11 @@ class Model:
             return None
         return ops.image_quality(ops.pixels_float(x, h, w), ops.pixels_float(recon, h, w), 255.0)
 
-    def _finish_metrics(self, x_shape, bits_z, bits_y, sse, msssim=None, sched=None, lams=None):
+    def _finish_metrics(self, x_shape, bits_z, bits_y, sse, msssim=None, sched=None, lams=None, wsse=None):
         """``sched`` = (scheduled_lr, sched_rd_lambda, tau) of the step the numbers belong to, when that is not the current one
         (metrics of an SGA step fetched later).  ``lams``: one lambda per image (SGA at a quantisation step): rd_loss =
-        bpp + mean_i(lambda_i D_i); every other scalar is unchanged."""
+        bpp + mean_i(lambda_i D_i); every other scalar is unchanged.  ``wsse``: each image's weighted squared error (SGA on a
+        step map): rd_loss = bpp + lambda mean_i(wsse_i / (H W C))."""
         n, h, w, c = x_shape
         num_pixels = np.float32(h * w)                                                  # :302
         bits_z = None if bits_z is None else bits_z.astype(np.float32)
@@ -444,6 +460,8 @@ class Model:
         if lams is not None:
             d = 1.0 - np.asarray(msssim, np.float64) if self._distortion == "ms_ssim" else mses.astype(np.float64)
             rd_loss = np.float32(bpp + np.float32((np.asarray(lams, np.float64) * d).mean()))
+        if wsse is not None:
+            rd_loss = np.float32(bpp + np.float32(float(lam) * (np.asarray(wsse, np.float64) / float(h * w * c)).mean()))
         if not np.isfinite(rd_loss):                                                    # :356
             raise capi.NonFiniteError(capi.ERR_NONFINITE, "rd_loss : Tensor had NaN/Inf values")
         metrics = Metrics.make()
@@ -706,7 +724,22 @@ class Model:
         the position's channels, with step_i the image's ``step`` (default 0) or the index ``target_bpp`` chooses (the report
         then adds map_bits, the 24 bits per run of the map counted in the prediction).  A map that varies inside an image is
         written as wire format 7; a constant one is the file of ``step=`` those indexes and all zeros the file of
-        ``compress(x)``, byte for byte.  ``entropy_coding.roi_offsets`` makes offsets from a pixel mask.  Excludes ``itinf``."""
+        ``compress(x)``, byte for byte.  ``entropy_coding.roi_offsets`` makes offsets from a pixel mask.  Excludes ``itinf`` at
+        the top level: refinement ON a map travels inside the dict, as ``step`` does.
+        ``itinf`` = dict(steps, ..., step=k | [k_i] | target_bpp=b | [b_i], step_offsets=off): SGA on the map
+        K_i[p] = clip(step_i + off[i, p]) -- every position is sampled on its own grid and priced under its own table, and the
+        distortion is the weighted MSE Dw_i = sum_pixels omega_i(pixel) (255 (x - x_hat))^2 / (H W C), omega = 1 / step_size(K_i[p])^2
+        for the pixels of position p's block (for a constant map this is lambda_i D_i of the paragraph above, and
+        it is the same stated modelling choice, not a measured optimum).  The candidates are judged by
+        ``coded_cost(x, latents, step=ks, step_offsets=off, weighted=True)`` and the file is
+        ``compress_latents(..., step=ks, step_offsets=off)``: never a worse file by that weighted J.  With ``target_bpp`` the base
+        indexes are chosen once, from the encoder's latents, over the map.  All-zero offsets are ``itinf=dict(steps, ...)`` and a
+        map constant per image is ``itinf=dict(steps, ..., step=those indexes)``, launch for launch and byte for byte.  The report
+        adds quant_step, weighted=True, sse_blocks (the chosen candidate's, as ``coded_cost`` returns them) and, with
+        ``target_bpp``, budget_bits, met, map_bits; a candidate is then eligible while its bits + the flushed lane states + map_bits
+        fit the budget.  MSE only (``distortion="ms_ssim"``
+        with a map: NotImplementedError); ``rd_lambda`` with a map: ValueError -- a weight per image and a weight per position are
+        not both defined."""
         self._check_step_arguments("compress", step, target_bpp, itinf, step_offsets)
         if itinf is not None:
             return self._compress_itinf(x, **itinf)
@@ -728,8 +761,8 @@ class Model:
         if step is not None and target_bpp is not None:
             raise ValueError(f"{where}: step and target_bpp exclude each other")
         if itinf is not None:
-            raise ValueError(f"{where}: step / target_bpp / step_offsets and itinf exclude each other (SGA on a step map is not "
-                             "implemented)")
+            raise ValueError(f"{where}: step / target_bpp / step_offsets and itinf exclude each other at the top level (they travel "
+                             "inside the itinf dict)")
         if self._precision != "fp32":
             raise NotImplementedError(f"{where}(step / target_bpp / step_offsets) runs in precision 'fp32', not {self._precision!r}: "
                                       "the pre-split dequantisation is not extended")
@@ -740,7 +773,7 @@ class Model:
             raise NotImplementedError("step_offsets_shape: a factorized-prior model takes no step_offsets; mean-scale hyperprior models only")
         return tuple(int(v) for v in self._get_codec().latent_shapes(int(H), int(W))[4:])
 
-    def coded_cost(self, x, latent_rvs=None, step=None, lam=None, step_offsets=None):
+    def coded_cost(self, x, latent_rvs=None, step=None, lam=None, step_offsets=None, weighted=False):
         """Per image, the cost of what ``decompress`` will output for ``latent_rvs`` (None: the encoder's latents of x) coded at
         ``step`` (None: step 1; a ladder index or one per image as in ``compress``), without
         writing a file: dict of float64 arrays [n] -- ``bits_z`` / ``bits_y`` = ``entropy_coding.rans_cost`` of the symbols the
@@ -748,8 +781,25 @@ class Model:
         rounding slack, DESIGN.md 4.7, are not in it), ``bits`` their sum, ``sse`` the integer SSE of the decoded uint8 pixels,
         ``D`` = the MSE of those pixels on the 0-255 scale (``distortion="ms_ssim"``: 1 - (MS-)SSIM of them, and ``msssim``),
         ``J`` = bits / (H W) + ``lam`` * D with ``lam`` the scheduled rd_lambda (``lam`` given: one weight per image instead, as
-        ``compress(x, itinf=dict(step=...))`` judges its candidates).  ``step_offsets``: as in ``compress``.  One host read-back."""
+        ``compress(x, itinf=dict(step=...))`` judges its candidates).  ``step_offsets``: as in ``compress``.  One host read-back.
+        ``weighted`` (False: the result above, key for key; True needs ``step`` and / or ``step_offsets``, MSE, and no ``lam``):
+        the cost on the map K_i[p] = clip(step_i + step_offsets[i, p]) as ``compress(x, itinf=dict(step_offsets=...))`` judges its
+        candidates.  Adds ``sse_blocks`` [n, hb, wb] = the integer squared error of the decoded pixels per B x B pixel block
+        (``ops.block_sse``; B pixels per latent position, hb = ceil(H / B); same read-back),
+        ``D_w`` = sum_p omega_i(p) sse_blocks[i, p] / (H W C) with omega = ``entropy_coding.position_weights`` (float64, on the
+        host), and ``J`` = bits / (H W) + lambda D_w with the scheduled rd_lambda.
+        ``sse_blocks`` is also a region-of-interest metric.  The PSNR of the decoded pixels inside a block mask (bool [hb, wb],
+        e.g. ``step_offsets[i, :hb, :wb] == inside``; edge blocks hold fewer pixels, so count them):
+            rows = np.minimum(B, H - B * np.arange(hb))[:, None]; cols = np.minimum(B, W - B * np.arange(wb))[None, :]
+            mse = sse_blocks[i][mask].sum() / (3.0 * (rows * cols)[mask].sum()); psnr = 10 * np.log10(255.0 ** 2 / mse)"""
         self._check_step_arguments("coded_cost", step, step_offsets=step_offsets)
+        if weighted:                                                  # every refusal before any launch
+            if step is None and step_offsets is None:
+                raise ValueError("coded_cost(weighted=True) needs step and / or step_offsets: the weights are those of a step map")
+            if self._distortion == "ms_ssim":
+                raise NotImplementedError("coded_cost(weighted=True): the weighted distortion is MSE, not distortion='ms_ssim'")
+            if lam is not None:
+                raise ValueError("coded_cost(weighted=True): lam (a weight per image) and a weight per position are not both defined")
         x = self._as_device_images(x)
         n, h, w, c = x.shape
         ssim = self._distortion == "ms_ssim"
@@ -760,12 +810,22 @@ class Model:
         if step_offsets is not None:
             from ..entropy_coding import check_offsets
             kw["step_offsets"] = check_offsets(step_offsets, n, *codec.latent_shapes(h, w)[4:])       # ValueError before any launch
+        if weighted:
+            from ..entropy_coding import check_steps, index_map, position_weights
+            lh, lw = codec.latent_shapes(h, w)[4:]
+            block = self._position_block(h, w)
+            offs = kw.get("step_offsets")
+            omega = position_weights(index_map(check_steps(0 if step is None else step, n),
+                                               np.zeros((n, lh, lw), np.int8) if offs is None else offs))
         with torch.cuda.device(self.device):
             if latent_rvs is None:
                 latent_rvs = self.infer_latent_rvs(x)
             cost_z, cost_y, px, sse = codec.latents_cost(*[rv.loc for rv in latent_rvs.uq], x, **kw)
             rows = [torch.zeros_like(cost_y) if cost_z is None else cost_z, cost_y, sse]
             parts = [torch.stack(rows).to(torch.float64).flatten()]   # integers below 2^53: exact
+            if weighted:                                              # uint32 -> float64 through int64: exact
+                blocks = ops.block_sse(x, px, block)
+                parts.append((blocks.view(torch.int32).to(torch.int64) & 0xFFFFFFFF).to(torch.float64).flatten())
             if ssim:
                 sums, counts, single = ops.image_quality_launch(ops.pixels_float(x, h, w), px.to(torch.float32), 255.0)
                 parts.append(sums.flatten())
@@ -780,9 +840,23 @@ class Model:
             out["msssim"] = ops.image_quality_finish(host[3 * n:].reshape(tuple(sums.shape)), counts, single)
             out["D"] = 1.0 - out["msssim"]
         out["J"] = out["bits"] / float(h * w) + out["lam"] * out["D"]
+        if weighted:
+            out["sse_blocks"] = np.rint(host[3 * n:]).astype(np.int64).reshape(tuple(blocks.shape))
+            out["D_w"] = weighted_distortion(out["sse_blocks"], omega, h * w * c)
+            out["J"] = out["bits"] / float(h * w) + out["lam"] * out["D_w"]
         return out
 
-    def _compress_itinf(self, x, steps, seed=0, check_every=None, step=None, rd_lambda=None, target_bpp=None):
+    def _position_block(self, H, W):
+        """B: the pixels per latent position along each side, the padded image size over the latent size
+        (``Codec.latent_shapes``; 16 for the shipped configs).  ValueError where that division is not exact."""
+        f = self.downsample_factor
+        hp, wp = -(-int(H) // f) * f, -(-int(W) // f) * f
+        lh, lw = self._get_codec().latent_shapes(int(H), int(W))[4:]
+        if hp % lh or wp % lw or hp // lh != wp // lw:
+            raise ValueError(f"a {hp} x {wp} padded image over {lh} x {lw} latent positions: no whole, square pixel block per position")
+        return hp // lh
+
+    def _compress_itinf(self, x, steps, seed=0, check_every=None, step=None, rd_lambda=None, target_bpp=None, step_offsets=None):
         if self._latent_config["uq"].get("method", "unoise") != "sga":       # every refusal before any launch
             raise NotImplementedError("itinf_train_step implements latent_config uq.method == 'sga'")
         if self._precision != "fp32":
@@ -790,10 +864,16 @@ class Model:
         steps = int(steps)
         if steps < 0 or (check_every is not None and int(check_every) < 1):
             raise ValueError("compress(itinf=...): steps >= 0, check_every None or >= 1")
-        stepped = step is not None or target_bpp is not None or rd_lambda is not None
+        mapped = step_offsets is not None
+        stepped = mapped or step is not None or target_bpp is not None or rd_lambda is not None
         n = 1 if len(tuple(x.shape)) == 3 else int(x.shape[0])
-        budgets = None
-        if stepped:
+        budgets = info = None
+        if mapped:
+            from ..entropy_coding import check_budgets
+            info = self._itinf_map_of(tuple(x.shape), step, rd_lambda, step_offsets, target_bpp)
+            if target_bpp is not None:
+                budgets = check_budgets(target_bpp, n)
+        elif stepped:
             from ..entropy_coding import check_budgets
             if step is not None and target_bpp is not None:
                 raise ValueError("compress(itinf=...): step and target_bpp exclude each other")
@@ -804,6 +884,7 @@ class Model:
         if self._distortion == "ms_ssim":
             ops.msssim_scale_sizes(x.shape[1], x.shape[2])
         codec = self._get_codec()
+        kmap = None
         if not stepped:
             self.initialize_itinf(x)
             cost_kw = lat_kw = {}
@@ -813,16 +894,30 @@ class Model:
             flushed = float(codec.flushed_bits(H, W))
             self.initialize_itinf(x)
             control = None
+            base = info["steps"] if mapped else None
             if budgets is not None:             # the steps of compress(x, target_bpp=b): chosen from the encoder's latents, once
                 budgets = budgets * float(H * W)
+                offs = info["offsets"] if mapped and info["offsets"].any() else None      # all zero: today's rate control
                 with torch.cuda.device(self.device):
-                    control = codec._rate_control(*[rv.loc.contiguous() for rv in self.latent_rvs.uq], H, W, budgets)[0]
-                quant = self._itinf_quant_of(n, [r["step_chosen"] for r in control], rd_lambda)
-            self._set_itinf_quant(quant)
-            ks = [0] * n if quant is None else quant["steps"]
-            lams = step_lambdas(self._rd_lambda, ks, rd_lambda)
-            lat_kw = dict(step=ks) if any(ks) else {}
-            cost_kw = dict(lat_kw, lam=lams)                              # J at each image's own step and weight
+                    control = codec._rate_control(*[rv.loc.contiguous() for rv in self.latent_rvs.uq], H, W, budgets, offs)[0]
+                base = [r["step_chosen"] for r in control]
+                if not mapped:
+                    quant = self._itinf_quant_of(n, base, rd_lambda)
+            if mapped:                          # Codec._quant's routing: only a map that varies inside an image is a map
+                uniform, kmap = codec._quant(base, info["offsets"], n, H, W)
+                if kmap is None:
+                    quant = self._itinf_quant_of(n, 0 if uniform is None else uniform, None)
+            if kmap is None:
+                self._set_itinf_quant(quant)
+                ks = [0] * n if quant is None else quant["steps"]
+                lams = step_lambdas(self._rd_lambda, ks, rd_lambda)
+                lat_kw = dict(step=ks) if any(ks) else {}
+                cost_kw = dict(lat_kw, lam=lams)                              # J at each image's own step and weight
+            else:
+                self._set_itinf_map(dict(kmap=kmap, block=info["block"]))
+                ks = base
+                lat_kw = dict(step=ks, step_offsets=info["offsets"])
+                cost_kw = dict(lat_kw, weighted=True)                         # J with the weight on every position's pixels
 
         def cost_of(latents):
             return self.coded_cost(x, latents, **cost_kw)
@@ -831,26 +926,37 @@ class Model:
             start = cost_of(self.latent_rvs)
             best = [rv.loc.clone() for rv in self.latent_rvs.uq]
             j_best, bits_best, step_best = start["J"].copy(), start["bits"].copy(), np.zeros(n, np.int64)
+            blocks_best = start["sse_blocks"].copy() if kmap is not None else None
             met = None if budgets is None else np.array([r["met"] for r in control], bool)
+            room = budgets                      # what a candidate's bits + flushed states may reach: the budget less the map's records
+            if budgets is not None and "map_bits" in control[0]:
+                room = budgets - np.array([r["map_bits"] for r in control], np.float64)
             for done in range(1, steps + 1):
                 self.itinf_train_step(x, seed=seed, fetch=False)
                 if done != steps and (check_every is None or done % int(check_every)):
                     continue
                 cand = cost_of(self.latent_rvs)
                 # strictly better only: the encoder's latents win a tie
-                for i in np.nonzero(candidate_wins(cand["J"], cand["bits"], j_best, bits_best, budgets, flushed, met))[0]:
+                for i in np.nonzero(candidate_wins(cand["J"], cand["bits"], j_best, bits_best, room, flushed, met))[0]:
                     for keep, rv in zip(best, self.latent_rvs.uq):
                         keep[i].copy_(rv.loc[i])
                     j_best[i], bits_best[i], step_best[i] = cand["J"][i], cand["bits"][i], done
+                    if blocks_best is not None:
+                        blocks_best[i] = cand["sse_blocks"][i]
             blob = codec.compress_latents(*best, x.shape[1:3], **lat_kw)
         self.last_compress_latents = LatentRVCollection(uq=tuple(UQLatentRV(t) for t in best))
         self.last_compress_report = [dict(step_chosen=int(step_best[i]), J_start=float(start["J"][i]), J_chosen=float(j_best[i]),
                                           bits_start=float(start["bits"][i]), bits_chosen=float(bits_best[i])) for i in range(n)]
         if stepped:
             for i, r in enumerate(self.last_compress_report):
-                r.update(quant_step=int(ks[i]), lam=float(lams[i]))
+                if kmap is None:
+                    r.update(quant_step=int(ks[i]), lam=float(lams[i]))
+                else:
+                    r.update(quant_step=int(ks[i]), weighted=True, sse_blocks=blocks_best[i].copy())
                 if budgets is not None:
                     r.update(budget_bits=float(budgets[i]), met=bool(met[i]))
+                    if "map_bits" in control[i]:
+                        r.update(map_bits=float(control[i]["map_bits"]))
         return blob
 
     def compress_many(self, xs):
@@ -884,17 +990,30 @@ class Model:
         return metrics
 
     # -- iterative inference (reference :389-413, common/itinf_lib.py:26-93) ----------------------------
-    def initialize_itinf(self, image_batch, step=None, rd_lambda=None):
+    def initialize_itinf(self, image_batch, step=None, rd_lambda=None, step_offsets=None):
         """latent_rvs = trainable copy of the encoder's latents; fresh Adam state (:389-395).
         ``step`` (a ladder index, or one per image) / ``rd_lambda`` (a number, or one per image; default
         lambda / step_size(k_i)^2): the steps that follow descend the loss at those quantisation steps,
         mean_B(bits_i) / (H W) + (1 / n) sum_i lambda_i D_i (sga.SGAEngine.loss_and_grads(quant=...)).  Every index 0
-        and no ``rd_lambda``: the steps of before, launch for launch."""
+        and no ``rd_lambda``: the steps of before, launch for launch.
+        ``step_offsets`` (integers [n, h, w] as in ``compress``): the steps that follow descend the loss on the map
+        K_i[p] = clip(step_i + step_offsets[i, p]), mean_B(bits_i) / (H W) + (lambda / n) sum_i Dw_i with the weight
+        1 / step_size(K_i[p])^2 on the pixels of position p (sga.SGAEngine.loss_and_grads(quant_map=...)); MSE only,
+        and ``rd_lambda`` is refused with it.  All-zero offsets are the steps of before and a map constant per image those of
+        ``step`` = its indexes, launch for launch; only a map that varies inside an image takes the map kernels."""
         from ..sga import SGAEngine
         if self._optimizer_config.get("global_clipnorm") is not None:
             raise NotImplementedError("gradient clipping is not used by the reference's itinf config")
         shape = tuple(image_batch.shape)
-        quant = self._itinf_quant_of(1 if len(shape) == 3 else shape[0], step, rd_lambda)    # every refusal before any launch
+        n = 1 if len(shape) == 3 else shape[0]
+        mapq = None
+        if step_offsets is None:
+            quant = self._itinf_quant_of(n, step, rd_lambda)            # every refusal before any launch
+        else:
+            info = self._itinf_map_of(shape, step, rd_lambda, step_offsets)
+            uniform, kmap = self._get_codec()._quant(info["steps"], info["offsets"], n, int(shape[-3]), int(shape[-2]))
+            quant = None if kmap is not None else self._itinf_quant_of(n, 0 if uniform is None else uniform, None)
+            mapq = None if kmap is None else dict(kmap=kmap, block=info["block"])
         if self._distortion == "ms_ssim":                               # ValueError where the loss is not computable
             ops.msssim_scale_sizes(*tuple(image_batch.shape)[1:3])
         self.latent_rvs = self.infer_latent_rvs(image_batch).get_trainable_copy()
@@ -904,6 +1023,39 @@ class Model:
         self._itinf_step = 0
         self._itinf_pending = None
         self._set_itinf_quant(quant)
+        self._set_itinf_map(mapq)
+
+    def _itinf_map_of(self, shape, step, rd_lambda, step_offsets, target_bpp=None):
+        """The host half of SGA on a step map (``initialize_itinf(step_offsets=)``, ``compress(itinf=dict(step_offsets=))``): every
+        refusal, before any launch.  -> dict(steps = the n base indexes, offsets int8 [n, h, w], block = pixels per position)."""
+        from ..entropy_coding import check_offsets, check_steps
+        if self.factorized:
+            raise NotImplementedError("SGA on a step map (step_offsets): mean-scale hyperprior models only")
+        if self._precision != "fp32":
+            raise NotImplementedError(f"SGA on a step map runs in precision 'fp32', not {self._precision!r}")
+        if self._distortion == "ms_ssim":
+            raise NotImplementedError("SGA on a step map descends the weighted MSE: distortion='ms_ssim' with step_offsets is not implemented")
+        if rd_lambda is not None:
+            raise ValueError("rd_lambda and step_offsets exclude each other: a weight per image and a weight per position are not both defined")
+        if step is not None and target_bpp is not None:
+            raise ValueError("compress(itinf=...): step and target_bpp exclude each other")
+        n = 1 if len(shape) == 3 else int(shape[0])
+        H, W = int(shape[-3]), int(shape[-2])
+        ks = check_steps(0 if step is None else step, n)
+        offs = check_offsets(step_offsets, n, *self._get_codec().latent_shapes(H, W)[4:])
+        return dict(steps=ks, offsets=offs, block=self._position_block(H, W))
+
+    def _set_itinf_map(self, mapq):
+        """``mapq`` = dict(kmap = absolute indexes int8 [n, h, w] on the host, block) or None: the device tensors of the map
+        kernels (the map, the coder's step table, the float32 position weights), one small upload each."""
+        if mapq is not None:
+            from ..entropy_coding import position_weights
+            codec = self._get_codec()
+            with torch.cuda.device(self.device):
+                mapq["tensors"] = (codec._map_tensor(mapq["kmap"]), codec._map_lut(),
+                                   ops.to_device(position_weights(mapq["kmap"]), self.device), int(mapq["block"]))
+            self._itinf_quant = None
+        self._itinf_map = mapq
 
     def _itinf_quant_of(self, n, step, rd_lambda):
         """The host half of ``initialize_itinf(step=, rd_lambda=)``: the refusals, the ladder indexes and each image's lambda.
@@ -948,37 +1100,43 @@ class Model:
         lr = self._scheduled_lr
         locs = [rv.loc for rv in self.latent_rvs.uq]                     # (z_loc, y_loc); the factorized model: (y_loc,)
         q = getattr(self, "_itinf_quant", None)
+        qm = getattr(self, "_itinf_map", None)
         with torch.cuda.device(self.device):
-            quant = None if q is None else q["tensors"]
+            quant = {} if q is None else dict(quant=q["tensors"])
+            if qm is not None:
+                quant = dict(quant_map=qm["tensors"])
             r = self._sga.loss_and_grads(x, locs[0] if len(locs) == 2 else None, locs[-1], tau, self._scheduled_rd_lambda,
                                          step=self._itinf_step, seed=seed,
                                          noise_z=None if noise is None else noise[0],
-                                         noise_y=None if noise is None else noise[-1], **({} if quant is None else dict(quant=quant)))
+                                         noise_y=None if noise is None else noise[-1], **quant)
             t = self._itinf_step + 1
             grads = [r["g_z"], r["g_y"]] if len(locs) == 2 else [r["g_y"]]
             for p, g, st in zip(locs, grads, self._adam):
                 ops.adam_step(p, g, st["m"], st["v"], lr, t, self._optimizer_config.get("beta_1", 0.9),
                               self._optimizer_config.get("beta_2", 0.999), self._optimizer_config.get("epsilon", 1e-7))
             # the metrics depend on (step, lr, lambda, tau) of THIS step: keep them with the device scalars
-            rows = [r["bits_z"], r["bits_y"], r["sse"]] + ([r["msssim"]] if "msssim" in r else [])
+            rows = [r["bits_z"], r["bits_y"], r["sse"]] + ([r["msssim"]] if "msssim" in r else []) + ([r["wsse"]] if "wsse" in r else [])
             self._itinf_pending = dict(dev=torch.stack(rows), shape=tuple(x.shape), two=len(locs) == 2,
                                        scalars=(self._scheduled_lr, self._scheduled_rd_lambda, tau),
-                                       lams=None if q is None else q["lam"])
+                                       lams=None if q is None or qm is not None else q["lam"], weighted="wsse" in r)
         self._itinf_step += 1
         self.last_grads = tuple(grads)
         return self.itinf_last_metrics() if fetch else None
 
     def itinf_last_metrics(self):
         """Metrics of the most recent ``itinf_train_step`` (one device -> host copy; raises if a stream-K launch since the last
-        check was flagged)."""
+        check was flagged).  On a step map (``initialize_itinf(step_offsets=)``) rd_loss = bpp + lambda mean_i(Dw_i), the loss
+        descended; mse / psnr stay unweighted and every other key is unchanged."""
         pend = getattr(self, "_itinf_pending", None)
         if pend is None:
             raise RuntimeError("no SGA step has run since initialize_itinf")
         with torch.cuda.device(self.device):
             host = pend["dev"].cpu().numpy()
             ops.check_conv_status()
+        wsse = host[-1] if pend.get("weighted") else None               # the last row; (MS-)SSIM and a map exclude each other
         _, metrics = self._finish_metrics(pend["shape"], host[0] if pend["two"] else None, host[1], host[2],
-                                          msssim=host[3] if len(host) > 3 else None, sched=pend["scalars"], lams=pend.get("lams"))
+                                          msssim=host[3] if len(host) > 3 and wsse is None else None, sched=pend["scalars"],
+                                          lams=pend.get("lams"), wsse=wsse)
         return metrics
 
     def itinf_validation_step(self, image_batch, training=False) -> Metrics:

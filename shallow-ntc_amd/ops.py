@@ -1169,6 +1169,24 @@ def pixels_sse(x, x_hat, want_pixels=False):
     return sse, px
 
 
+def block_sse(x, pixels, block):
+    """The integer squared error of decoded uint8 ``pixels`` [n, h, w, c] against ``x`` quantised as ``pixels_sse`` quantises it,
+    per ``block`` x ``block`` pixel block (ragged at the right and bottom edges): -> uint32 [n, ceil(h / block), ceil(w / block)]
+    on the device; exact, and its per-image sums are ``pixels_sse``'s.  block^2 c 255^2 must stay below 2^32 (the library
+    refuses anything else)."""
+    _check_nhwc(x)
+    n, h, w, c = x.shape
+    block = int(block)
+    if not (isinstance(pixels, torch.Tensor) and pixels.dtype == torch.uint8 and tuple(pixels.shape) == (n, h, w, c)
+            and pixels.is_contiguous() and pixels.device == x.device):
+        raise ValueError(f"block_sse: pixels uint8 {(n, h, w, c)} on the images' device")
+    if block < 1:
+        raise ValueError("block_sse: block >= 1")
+    out = torch.empty((n, -(-h // block), -(-w // block)), dtype=torch.uint32, device=x.device)
+    capi.call("sntc_block_sse", _ptr(x), _ptr(pixels), n, h, w, c, block, _ptr(out), _stream())
+    return out
+
+
 def float_sse(x, x_hat):
     _check_nhwc(x)
     _check_nhwc(x_hat, x.shape[-1])
@@ -1422,6 +1440,46 @@ def sga_normal_step_bwd(g_ytilde, sprime, dbits_dv, dbits_draw, weight, quant):
     return g_y, g_h
 
 
+def sga_normal_step_map_fwd(y_loc, hyper, tau, kmap, lut, noise=None, seed=0, step=0):
+    """``sga_normal_step_fwd`` with one ladder index per latent POSITION: ``kmap`` int8 [n, h, w] on the device (any byte: the
+    kernel clamps it to the ladder), ``lut`` = entropy_coding.step_lut.  At k = kmap[image, position] the sample lies on the grid
+    of step_size(k) and the rate is that of the table k places down the ladder; a map constant per image gives
+    ``sga_normal_step_fwd``'s outputs at those indexes, bit for bit.
+    -> (y_tilde = fma(step_size(k), v, mu), sprime = d v / d u, dbits_dv, dbits_draw, bits[n])."""
+    _check_nhwc(y_loc)
+    c = y_loc.shape[-1]
+    _check_nhwc(hyper, 2 * c)
+    n, hw = y_loc.shape[0], y_loc.shape[1] * y_loc.shape[2]
+    if tuple(hyper.shape[:3]) != tuple(y_loc.shape[:3]):
+        raise ValueError(f"hyper-synthesis output {tuple(hyper.shape)} does not match latents {tuple(y_loc.shape)}")
+    if noise is not None and not (isinstance(noise, torch.Tensor) and noise.is_cuda and noise.dtype == torch.float32
+                                  and noise.is_contiguous() and tuple(noise.shape) == tuple(y_loc.shape) + (2,)):
+        raise ValueError("noise: contiguous float32 Gumbel pairs shaped like y_loc + (2,)")
+    _check_step_map(y_loc, kmap, lut, "sga_normal_step_map_fwd")
+    yt, sp, dv, dr = (torch.empty_like(y_loc) for _ in range(4))
+    bits = torch.empty((n,), dtype=torch.float64, device=y_loc.device)
+    capi.call("sntc_sga_normal_step_map_fwd", _ptr(y_loc), _ptr(hyper), n, hw, c, float(tau), _ptr(noise), int(seed), int(step),
+              _ptr(kmap), _ptr(lut), _ptr(yt), _ptr(sp), _ptr(dv), _ptr(dr), _ptr(bits), _stream())
+    return yt, sp, dv, dr, bits
+
+
+def sga_normal_step_map_bwd(g_ytilde, sprime, dbits_dv, dbits_draw, weight, kmap, lut):
+    """``sga_normal_step_bwd`` with one ladder index per latent position and no per-image weight on the distortion gradient
+    (on a map the weight sits on the pixels: ``distortion_grad_weighted``).  -> (g_yloc, g_hyper[.., 2C])."""
+    _check_nhwc(g_ytilde)
+    n, h, w, c = g_ytilde.shape
+    for t in (sprime, dbits_dv, dbits_draw):
+        _check_nhwc(t, c)
+        if tuple(t.shape) != tuple(g_ytilde.shape):
+            raise ValueError(f"sga_normal_step_map_bwd: {tuple(t.shape)} does not match the gradient {tuple(g_ytilde.shape)}")
+    _check_step_map(g_ytilde, kmap, lut, "sga_normal_step_map_bwd")
+    g_y = torch.empty_like(g_ytilde)
+    g_h = torch.empty((n, h, w, 2 * c), dtype=torch.float32, device=g_ytilde.device)
+    capi.call("sntc_sga_normal_step_map_bwd", _ptr(g_ytilde), _ptr(sprime), _ptr(dbits_dv), _ptr(dbits_draw), float(weight),
+              n, h * w, c, _ptr(kmap), _ptr(lut), _ptr(g_y), _ptr(g_h), _stream())
+    return g_y, g_h
+
+
 def sga_chain(g, dbits, sprime, weight):
     out = torch.empty_like(g)
     capi.call("sntc_sga_chain", _ptr(g), _ptr(dbits), _ptr(sprime), float(weight), g.numel(), _ptr(out), _stream())
@@ -1468,6 +1526,28 @@ def distortion_grad(x, x_hat, scale):
     capi.call("sntc_distortion_grad", _ptr(x), _ptr(x_hat), n, h, w, c, x_hat.shape[1], x_hat.shape[2], float(scale),
               _ptr(g), _ptr(sse), _stream())
     return g, sse
+
+
+def distortion_grad_weighted(x, x_hat, scale, weights, block):
+    """``distortion_grad`` with a weight per ``block`` x ``block`` pixels: ``weights`` float32 [n, hb, wb] on the device covering
+    x_hat (hb block >= its height, wb block >= its width); pixel (r, s) takes weights[image, r // block, s // block].
+    -> (g_xhat = (scale weight) (x_hat - x), zero in the padded margin; sse[n] float64, UNWEIGHTED, as ``distortion_grad`` leaves
+    it; wsse[n] float64 = sum weight (255 (x - x_hat))^2)."""
+    _check_nhwc(x)
+    _check_nhwc(x_hat, x.shape[-1])
+    n, h, w, c = x.shape
+    block = int(block)
+    if not (isinstance(weights, torch.Tensor) and weights.dtype == torch.float32 and weights.dim() == 3 and weights.shape[0] == n
+            and weights.is_contiguous() and weights.device == x.device):
+        raise ValueError(f"distortion_grad_weighted: weights float32 [{n}, hb, wb] on the images' device")
+    hb, wb = int(weights.shape[1]), int(weights.shape[2])
+    if x_hat.shape[0] != n or block < 1 or hb * block < x_hat.shape[1] or wb * block < x_hat.shape[2]:
+        raise ValueError(f"distortion_grad_weighted: {hb} x {wb} weights of {block} pixels do not cover {tuple(x_hat.shape)}")
+    g = torch.empty_like(x_hat)
+    sums = torch.empty((2, n), dtype=torch.float64, device=x.device)
+    capi.call("sntc_distortion_grad_weighted", _ptr(x), _ptr(x_hat), n, h, w, c, x_hat.shape[1], x_hat.shape[2], float(scale),
+              _ptr(weights), hb, wb, block, _ptr(g), _ptr(sums[0]), _ptr(sums[1]), _stream())
+    return g, sums[0], sums[1]
 
 
 def two_layer_tail_bwd(t, g_h, ch, has_res, act_kind, beta, gamma, cp, param_operands=False):

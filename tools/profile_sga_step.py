@@ -3,13 +3,19 @@
 
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/profile_sga_step.py kernels
     python tools/profile_sga_step.py compress [--out profiles/sga_step.json] [--steps 100]
+    python tools/profile_sga_step.py map [--out profiles/sga_step_map.json] [--steps 100]
 
 ``kernels``: the kernel pairs of step 1 and of a step on 18 x 32 x 48 x 320 latents at ladder index 0 (the same arithmetic on the
 same numbers: what differs is the layout), alternating, 30 calls each after 3 of warm-up, to be read from a kernel trace taken in
 a run of its own (prints the bytes each launch moves).
 ``compress``: ``compress(x, itinf=dict(steps, step=k))`` for k in (-6, 0, +6) on the tests' fixture (2 x 128 x 128) and on one
 512 x 768 image, ``two_layer_syn`` with spread scale biases and RANDOM weights: J_start -> J_chosen, bits, and the wall clock
-against ``compress(x, step=k)``."""
+against ``compress(x, step=k)``.
+``map``: SGA on a step map (``sga_normal_step_map_*``, ``distortion_grad_weighted``, ``block_sse``) next to the uniform-step path, on
+the same two image sets: the uniform path is ``step=-6``, the map is -6 on the centred half-size rectangle of positions and +6
+around it (``step=-6`` with offsets 0 / +12).  Per SGA step (``itinf_train_step(fetch=False)``, synchronised host wall clock, the two
+variants alternating on two models of the same weights, median of ``--calls``) and per ``compress(x, itinf=...)`` call (median of 3,
+alternating).  RANDOM weights: the times are what is measured, not a rate-distortion gain."""
 import argparse
 import json
 import sys
@@ -103,15 +109,79 @@ def compress(args):
     return 0
 
 
+def centred_offsets(model, n, H, W, inside=0, outside=12):
+    h, w = model.step_offsets_shape(H, W)
+    off = np.full((n, h, w), outside, np.int8)
+    off[:, h // 4:h // 4 + h // 2, w // 4:w // 4 + w // 2] = inside
+    return off
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t)
+
+
+def step_map(args):
+    dev = torch.device("cuda:0")
+    models = dict(uniform=spread_model(dev), map=spread_model(dev))      # the same weights twice: each keeps its own SGA state
+    out = dict(device=torch.cuda.get_device_name(0), weights="RANDOM (two_layer_syn, spread scale biases): no rate-distortion gain on a "
+               "trained model is claimed or measured here", steps=args.steps, base_step=-6,
+               map="K = -6 on the centred half-size rectangle of positions, +6 around it (step=-6, offsets 0 / +12)",
+               timer=f"host wall clock, synchronised; the two variants alternate; SGA step: median of {args.calls} after 3 of warm-up; "
+                     "compress(itinf): median of 3 after one warm-up call", cases=[])
+    sets = {"fixture 2x128x128": torch.from_numpy(data_lib.normalize_image(data_lib.synthetic_images(2, 128, 128, seed=21))).to(dev),
+            "1x512x768": torch.from_numpy(data_lib.normalize_image(data_lib.synthetic_images(1, 512, 768, seed=11))).to(dev)}
+    for name, x in sets.items():
+        n, H, W = x.shape[0], x.shape[1], x.shape[2]
+        off = centred_offsets(models["map"], n, H, W)
+        kw = dict(uniform=dict(step=-6), map=dict(step=-6, step_offsets=off))
+        for which, model in models.items():
+            model.initialize_itinf(x, **kw[which])
+        assert models["map"]._itinf_map is not None and models["uniform"]._itinf_map is None
+        times = dict(uniform=[], map=[])
+        for i in range(args.calls + 3):
+            for which, model in models.items():
+                d = timed(lambda: model.itinf_train_step(x, seed=3, fetch=False))
+                if i >= 3:
+                    times[which].append(d)
+        row = dict(images=name, positions=list(off.shape[1:]), inside=int((off[0] == 0).sum()),
+                   sga_step_ms={k: round(float(np.median(v)), 3) for k, v in times.items()},
+                   sga_step_ms_min_max={k: [round(min(v), 3), round(max(v), 3)] for k, v in times.items()})
+        itinf = {k: dict(steps=args.steps, seed=3, **v) for k, v in kw.items()}
+        times = dict(uniform=[], map=[])
+        for i in range(4):
+            for which, model in models.items():
+                d = timed(lambda: model.compress(x, itinf=itinf[which]))
+                if i >= 1:
+                    times[which].append(d)
+        row["compress_itinf_ms"] = {k: round(float(np.median(v)), 2) for k, v in times.items()}
+        for which, model in models.items():
+            rep = model.last_compress_report
+            row[which] = dict(step_chosen=[r["step_chosen"] for r in rep], J_start=[round(r["J_start"], 6) for r in rep],
+                              J_chosen=[round(r["J_chosen"], 6) for r in rep], bits_start=[r["bits_start"] for r in rep],
+                              bits_chosen=[r["bits_chosen"] for r in rep])
+        out["cases"].append(row)
+        print(json.dumps(row), flush=True)
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
+    print("wrote", args.out)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["kernels", "compress"])
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "sga_step.json"))
+    ap.add_argument("mode", choices=["kernels", "compress", "map"])
+    ap.add_argument("--out", default=None, help="default: profiles/sga_step.json (compress), profiles/sga_step_map.json (map)")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--k", type=int, default=0, help="kernels: the ladder index of every image")
     args = ap.parse_args()
-    return kernels(args) if args.mode == "kernels" else compress(args)
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / ("sga_step_map.json" if args.mode == "map" else "sga_step.json"))
+    return dict(kernels=kernels, compress=compress, map=step_map)[args.mode](args)
 
 
 if __name__ == "__main__":
