@@ -592,6 +592,25 @@ int sntc_step_map_ladder_cost(const float* y, const float* mu, int n, int64_t hw
                               const int8_t* offsets, const float* lut, const int32_t* base, int nsteps, const uint32_t* meta,
                               int ntables, int total_entries, const uint32_t* cost_q, uint64_t* cost, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The distortion side of the ladder (csrc/quant_step_ladder.hip, DESIGN.md 4.7 "quality target"): what every candidate step
+ *   DECODES to, in one pass.  The reference decodes y_hat = round(y - mu) + mu once per evaluation (mshyper/models.py:273-279);
+ *   here, per element and candidate j (1 <= nsteps <= 16), with the three rules above and nothing else,
+ *     s = (int)rintf((y - mu) * inv_step[j]),  y_hat[j][image][position][channel] = fmaf(step[j], (float)s, mu)
+ *   -- sntc_dequant_step of sntc_step_symbols at that step, bit for bit, without a symbol tensor.  The symbol is NOT clamped:
+ *   it is the one coded_cost decodes, not the file's 16-bit escape.  y_hat float [nsteps][n][hw][c]: candidate j is a contiguous
+ *   batch of n latents, so the candidates go through the decoder as ONE batch of nsteps n.  y and mu are read once (8 bytes per
+ *   element) and feed nsteps stores (4 nsteps bytes): a store stream, no atomics, no LDS.  inv_step / step float [nsteps] on the
+ *   device.  mu_stride is c or 2 c; 1 <= n <= 65535; any c >= 1.  16-byte loads and stores where y, mu and y_hat are 16-byte
+ *   aligned and c % 4 == 0, an element-wise path with the same result otherwise. */
+int sntc_step_ladder_dequant(const float* y, const float* mu, int n, int64_t hw, int c, int mu_stride, const float* inv_step,
+                             const float* step, int nsteps, float* y_hat, void* stream);
+/* The same over a map: candidate j (base int32 [nsteps] on the device) quantises position p at the index
+ *   clamp(base[j] + offsets[image][p], -32, 32), offsets int8 [n][hw], step and inverse step read from lut float [2][65] as in
+ *   sntc_step_map_symbols -- sntc_dequant_step_map of sntc_step_map_symbols on that map, bit for bit. */
+int sntc_step_map_ladder_dequant(const float* y, const float* mu, int n, int64_t hw, int c, int mu_stride, const int8_t* offsets,
+                                 const float* lut, const int32_t* base, int nsteps, float* y_hat, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * SSIM / MS-SSIM statistics (eval-only quality metrics, reference mshyper/models.py:321-336 ->
  *   tf.image.ssim / tf.image.ssim_multiscale).  Images are float NHWC holding pixel

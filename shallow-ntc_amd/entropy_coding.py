@@ -58,6 +58,7 @@ SCALE_FACTOR = (math.log(SCALE_MAX) - math.log(SCALE_MIN)) / (NUM_SCALES - 1.0)
 VERSION_STEP = 5                          # v3 + one signed byte per image: its quantisation step's index on the scale ladder
 STEP_MIN, STEP_MAX = -32, 32              # ladder indexes a file may carry (checked here; the kernels' id clamp absorbs any shift)
 LADDER_MAX = 16                           # candidate steps of one sntc_step_ladder_cost launch
+LADDER_DECODE_BYTES = 1 << 30             # candidate latents (y_hat) one decoder batch of ``Codec.ladder_distortion`` holds at the most
 VERSION_MAP = 7                           # v3 + the ladder index of every latent position, run-length coded
 OFFSET_MIN, OFFSET_MAX = -64, 64          # ``step_offsets`` a caller may pass: enough to cross the whole ladder either way
 RUN_MAX = 65535                           # positions one record of a v7 map covers at the most
@@ -129,6 +130,53 @@ def select_steps(bits, budget_bits, steps, map_bits=None):
         out.append(dict(step_chosen=k, bits_predicted=pred, budget_bits=float(budget), met=bool(fits)))
         if map_bits is not None:
             out[-1]["map_bits"] = float(map_bits[i])
+    return out
+
+
+def check_quality(target_psnr, n):
+    """``target_psnr`` in dB (a number, or a sequence of n numbers) -> float64 [n]; ValueError on anything else."""
+    try:
+        t = np.asarray(target_psnr, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"target_psnr must be a finite number or {n} of them, not {target_psnr!r}") from None
+    if t.ndim == 0:
+        t = np.full(n, float(t))
+    if t.shape != (n,) or not np.isfinite(t).all():
+        raise ValueError(f"target_psnr must be a finite number or {n} of them, not {target_psnr!r}")
+    return t
+
+
+def quality_budgets(targets, H, W):
+    """PSNR targets in dB (``check_quality``) -> the largest squared error of the decoded uint8 pixels of an H x W RGB image
+    that still meets them, float64: 255^2 3 H W / 10^(target / 10).  Compared against the INTEGER SSE: sse <= budget."""
+    return 255.0 ** 2 * 3.0 * float(H) * float(W) / 10.0 ** (np.asarray(targets, np.float64) / 10.0)
+
+
+def psnr_of_sse(sse, elements):
+    """PSNR in dB of a squared error over ``elements`` = 3 H W pixel values on the 0-255 scale, float64 (inf at sse 0)."""
+    with np.errstate(divide="ignore"):
+        return 10.0 * np.log10(255.0 ** 2 * float(elements) / np.asarray(sse, np.float64))
+
+
+def select_quality(bits, sse, sse_budget, steps, elements=None):
+    """The quality-target rule, a pure function: ``bits`` [n, len(steps)] = what image i would pay at ladder index steps[j],
+    ``sse`` [n, len(steps)] = the integer squared error it would decode to there, ``sse_budget`` [n] (``quality_budgets``).
+    Per image, among the candidates with sse <= budget, the one with the FEWEST bits -- not the coarsest that qualifies: neither
+    row need be monotone -- and on equal bits the larger ladder index; STEP_MIN, met = False, where none qualifies.
+    ``elements`` (3 H W, if the caller has it): psnr_predicted of the chosen candidate's sse, else None.
+    -> list of dict(step_chosen, bits_predicted, sse_predicted, psnr_predicted, sse_budget, met)."""
+    bits, sse = np.asarray(bits, np.float64), np.asarray(sse, np.float64)
+    steps = [int(k) for k in steps]
+    if bits.ndim != 2 or bits.shape[1] != len(steps) or sse.shape != bits.shape or len(sse_budget) != bits.shape[0]:
+        raise ValueError("select_quality: bits and sse [n, len(steps)] and n budgets")
+    out = []
+    for brow, srow, budget in zip(bits, sse, sse_budget):
+        ok = [j for j in range(len(steps)) if srow[j] <= budget]
+        j = min(ok, key=lambda j: (brow[j], -steps[j])) if ok else (steps.index(STEP_MIN) if STEP_MIN in steps else None)
+        k = steps[j] if ok else STEP_MIN
+        b, e = (float(brow[j]), float(srow[j])) if j is not None else (float("nan"), float("nan"))
+        psnr = None if elements is None else float(psnr_of_sse(e, elements))
+        out.append(dict(step_chosen=k, bits_predicted=b, sse_predicted=e, psnr_predicted=psnr, sse_budget=float(budget), met=bool(ok)))
     return out
 
 
@@ -1021,6 +1069,70 @@ class Codec:
         with torch.cuda.device(self.m.device):
             return self._ladder(z_loc.contiguous(), y_loc.contiguous(), steps, offsets=offsets)
 
+    def ladder_distortion(self, z_loc, y_loc, x, steps, step_offsets=None, chunk_bytes=LADDER_DECODE_BYTES, pre=None):
+        """``latents_cost``'s integer SSE at EVERY ladder index of ``steps``: -> int64 [n, len(steps)] on the device, no host
+        synchronisation; column j is what ``latents_cost(z_loc, y_loc, x, step=steps[j], step_offsets=...)`` returns, exactly
+        (decoding is batch-invariant and the step rule is one header: the decoded SSE of a candidate is a well-defined integer).
+        The hyper-synthesis runs once; the candidates go through in chunks of min(LADDER_MAX, max(1, ``chunk_bytes`` // the
+        bytes of one candidate's y_hat)): per chunk ONE launch of csrc/quant_step_ladder.hip writes the dequantised latents of
+        its candidates, candidate-major, and ONE decoder batch of chunk n latents decodes them against the images repeated on
+        the device.  ``chunk_bytes`` bounds memory only: the result does not depend on it.  ``pre``: ``_hyper_of(z_loc)`` if
+        the caller has it."""
+        m = self.m
+        steps = check_steps(list(steps), len(steps))
+        if not steps:
+            raise ValueError("ladder_distortion: no candidate step")
+        if m._precision != "fp32":
+            raise NotImplementedError(f"quantisation steps run in precision 'fp32', not {m._precision!r}")
+        n, H, W = self._check_latents(z_loc, y_loc, x.shape[1:3])
+        offsets = None if step_offsets is None else check_offsets(step_offsets, n, *y_loc.shape[1:3])
+        with torch.cuda.device(m.device):
+            y = y_loc.contiguous()
+            _, hyper = self._hyper_of(z_loc.contiguous()) if pre is None else pre
+            chunk = min(LADDER_MAX, max(1, int(chunk_bytes) // (4 * y.numel())))
+            if offsets is None:
+                st, inv, _ = self._step_tensors(steps)
+            else:
+                off_d, bases = self._map_tensor(offsets), torch.tensor(steps, dtype=torch.int32).to(m.device)
+            sse = torch.empty((n, len(steps)), dtype=torch.int64, device=m.device)
+            for lo in range(0, len(steps), chunk):
+                k = min(chunk, len(steps) - lo)
+                if offsets is None:
+                    y_hat = ops.step_ladder_dequant(y, hyper, inv[lo:lo + k], st[lo:lo + k])
+                else:
+                    y_hat = ops.step_map_ladder_dequant(y, hyper, off_d, self._map_lut(), bases[lo:lo + k])
+                _, part = m._pixels(y_hat.view((k * n,) + tuple(y.shape[1:])), (H, W), x.repeat(k, 1, 1, 1))
+                sse[:, lo:lo + k] = part.view(k, n).t()
+            return sse
+
+    def rd_ladder(self, z, y, x, steps, offsets=None):
+        """Rate and distortion of every ladder index of ``steps`` for given latents: the ladder-cost launches, ``ladder_distortion``
+        and ONE read-back -> (cost_z int64 [n], cost_y int64 [n, S] in 2^-16 bit, sse int64 [n, S] as host arrays, ``_hyper_of(z)``
+        for the coding launches).  ``offsets`` (``check_offsets``): the candidates are bases of the map clip(base + offsets)."""
+        pre = self._hyper_of(z)
+        cost_z, cost_y = self._ladder(z, y, steps, pre, offsets)
+        sse = self.ladder_distortion(z, y, x, steps, offsets, pre=pre)
+        host = torch.cat([cost_z[:, None], cost_y, sse], dim=1).cpu().numpy()                                    # the one read-back
+        ops.check_conv_status()
+        S = len(steps)
+        return host[:, 0], host[:, 1:1 + S], host[:, 1 + S:], pre
+
+    def _quality_control(self, z, y, x, H, W, sse_budget, offsets=None):
+        """The pass of ``compress(x, target_psnr=...)`` on given latents: the whole ladder priced and decoded (``rd_ladder``), the
+        flushed lane states and the map's records counted as ``_rate_control`` counts them, ``select_quality``.
+        -> (the per-image report, ``_hyper_of(z)`` for the coding launches)."""
+        ladder = list(range(STEP_MIN, STEP_MAX + 1))
+        cost_z, cost_y, sse, pre = self.rd_ladder(z, y, x, ladder, offsets)
+        bits = (cost_z[:, None] + cost_y) / float(COST_UNIT) + float(self.flushed_bits(H, W))
+        map_bits = None if offsets is None else MAP_RECORD_BITS * count_runs(offsets)
+        if map_bits is not None:
+            bits = bits + map_bits.astype(np.float64)[:, None]
+        report = select_quality(bits, sse, sse_budget, ladder, elements=3 * H * W)
+        if map_bits is not None:
+            for r, b in zip(report, map_bits):
+                r["map_bits"] = float(b)
+        return report, pre
+
     def flushed_bits(self, H, W):
         """The lane states every image's streams flush, in bits: 32 per lane and stream (in the file, not in ``rans_cost``)."""
         c, cz, hz, wz, h, w = self.latent_shapes(H, W)
@@ -1028,23 +1140,31 @@ class Codec:
         sz, sy = _segments(ez), _segments(ey)
         return 32 * (sz * _lanes(-(-ez // sz)) + sy * _lanes(-(-ey // sy)))
 
-    def compress(self, x, step=None, target_bpp=None, step_offsets=None) -> bytes:
+    def compress(self, x, step=None, target_bpp=None, step_offsets=None, target_psnr=None) -> bytes:
         """``step`` / ``step_offsets``: as in ``compress_latents``; with ``target_bpp`` the offsets are added to the index rate
         control chooses, the candidates are priced over the map (``ladder_cost(..., step_offsets=...)``), and each image's
         prediction counts ``map_bits`` = 24 per maximal run of its offsets (an upper bound on the records written: clipping
         can only merge runs).  ``target_bpp`` (a number, or one per image): rate control -- per image the
         finest step of the whole ladder whose predicted bits (``ladder_cost`` + the flushed lane states; header and length
         fields not counted) are within target_bpp H W, STEP_MAX where none is.  One encoder pass, the ladder launches, one
-        read-back, the coding launches.  ``last_report``: per image step_chosen, bits_predicted, budget_bits, met."""
+        read-back, the coding launches.  ``last_report``: per image step_chosen, bits_predicted, budget_bits, met.
+        ``target_psnr`` in dB (a number, or one per image): the opposite question -- per image the step of the whole ladder
+        with the FEWEST predicted bits among those whose decoded pixels reach the target (integer SSE <= 255^2 3 H W /
+        10^(target / 10), ``ladder_distortion``: exactly what ``decompress`` will give, the 16-bit escape aside), STEP_MIN where
+        none does (``select_quality``).  One encoder pass, the ladder launches of both sides, one read-back, the coding launches;
+        the file is that of ``step=`` the chosen indexes.  ``last_report``: ``select_quality``'s rows (+ map_bits with offsets)."""
         m = self.m
         x = m._as_device_images(x)
         n, H, W = x.shape[0], int(x.shape[1]), int(x.shape[2])
-        if step is not None and target_bpp is not None:
-            raise ValueError("compress: step and target_bpp exclude each other")
+        if sum(v is not None for v in (step, target_bpp, target_psnr)) > 1:
+            raise ValueError("compress: step, target_bpp and target_psnr exclude each other")
         steps, kmap = self._quant(step, step_offsets, n, H, W)
         budgets, offsets = None, None
-        if target_bpp is not None:
-            budgets = check_budgets(target_bpp, n) * float(H * W)
+        if target_bpp is not None or target_psnr is not None:
+            if target_psnr is not None:
+                budgets = quality_budgets(check_quality(target_psnr, n), H, W)
+            else:
+                budgets = check_budgets(target_bpp, n) * float(H * W)
             if m._precision != "fp32":
                 raise NotImplementedError(f"quantisation steps run in precision 'fp32', not {m._precision!r}")
             if step_offsets is not None:
@@ -1055,7 +1175,10 @@ class Codec:
             z, y = lat.uq[0].loc.contiguous(), lat.uq[1].loc.contiguous()
             if budgets is None:
                 return self._finish([self._launch_latents(z, y, (H, W), steps, kmap=kmap)])[0]
-            self.last_report, pre = self._rate_control(z, y, H, W, budgets, offsets)
+            if target_psnr is not None:
+                self.last_report, pre = self._quality_control(z, y, x, H, W, budgets, offsets)
+            else:
+                self.last_report, pre = self._rate_control(z, y, H, W, budgets, offsets)
             chosen = [r["step_chosen"] for r in self.last_report]
             steps, kmap = self._quant(chosen, offsets, n, H, W)
             return self._finish([self._launch_latents(z, y, (H, W), steps, pre, kmap)])[0]

@@ -691,7 +691,7 @@ class Model:
             self._codec = Codec(self)
         return self._codec
 
-    def compress(self, x, itinf=None, step=None, target_bpp=None, step_offsets=None) -> bytes:
+    def compress(self, x, itinf=None, step=None, target_bpp=None, step_offsets=None, target_psnr=None) -> bytes:
         """Images -> self-contained bitstream (rANS over the integer CDF tables of both entropy models).
         ``itinf`` = dict(steps, seed=0, check_every=None): refine the latents of THESE images by SGA iterative inference first
         (``initialize_itinf`` + ``steps`` x ``itinf_train_step(x, seed=seed, fetch=False)`` under the model's own tau / learning-rate
@@ -739,27 +739,69 @@ class Model:
         ``target_bpp``, budget_bits, met, map_bits; a candidate is then eligible while its bits + the flushed lane states + map_bits
         fit the budget.  MSE only (``distortion="ms_ssim"``
         with a map: NotImplementedError); ``rd_lambda`` with a map: ValueError -- a weight per image and a weight per position are
-        not both defined."""
-        self._check_step_arguments("compress", step, target_bpp, itinf, step_offsets)
+        not both defined.
+        ``target_psnr`` in dB (a number, or one per image): the smallest file that still decodes to at least that PSNR -- per
+        image the step of the whole ladder with the fewest predicted bits among those whose decoded uint8 pixels have an integer
+        SSE <= 255^2 3 H W / 10^(target / 10), STEP_MIN (met = False) where none has.  The decoded SSE of all 65 steps comes
+        from ``rd_curve``'s passes (the candidates decoded as batches, exactly ``coded_cost``'s sse), the bits are those
+        ``target_bpp`` compares; the file is that of ``step=`` the chosen indexes, byte for byte (with ``step_offsets`` the
+        candidates are bases of the map and map_bits is counted, as for ``target_bpp``).  ``last_compress_report`` lists
+        step_chosen, bits_predicted, sse_predicted, psnr_predicted, sse_budget, met.  Excludes ``step``, ``target_bpp`` and
+        ``itinf``; inside the ``itinf`` dict it is not implemented."""
+        self._check_step_arguments("compress", step, target_bpp, itinf, step_offsets, target_psnr=target_psnr)
         if itinf is not None:
+            if "target_psnr" in itinf:
+                raise ValueError("compress: target_psnr is not implemented inside itinf")
             return self._compress_itinf(x, **itinf)
-        if step is None and target_bpp is None and step_offsets is None:
+        if step is None and target_bpp is None and step_offsets is None and target_psnr is None:
             return self._get_codec().compress(x)
         codec = self._get_codec()
-        blob = codec.compress(x, step=step, target_bpp=target_bpp, step_offsets=step_offsets)
-        if target_bpp is not None:
+        blob = codec.compress(x, step=step, target_bpp=target_bpp, step_offsets=step_offsets, target_psnr=target_psnr)
+        if target_bpp is not None or target_psnr is not None:
             self.last_compress_report = codec.last_report
         return blob
 
-    def _check_step_arguments(self, where, step, target_bpp=None, itinf=None, step_offsets=None):
+    def rd_curve(self, x, steps=None, step_offsets=None):
+        """The exact rate-distortion ladder of these images: what every ladder index of ``steps`` (None: the whole ladder,
+        STEP_MIN .. STEP_MAX) would cost in the file and decode to, from ONE encoder pass, the ladder-cost launches, the
+        candidates decoded as batches (``Codec.ladder_distortion``) and one read-back -- not one ``coded_cost`` per step.
+        -> dict(steps, bits [n, S] = ``coded_cost(x, step=steps[j], step_offsets=...)["bits"]`` + the flushed lane states (what
+        ``target_bpp`` compares), bpp = bits / (H W), sse [n, S] int64 = ``coded_cost``'s, exactly, psnr of it in dB,
+        bits_z [n], flushed_bits; with ``step_offsets`` also map_bits [n], the map's records, NOT in bits).
+        Mean-scale hyperprior models in precision 'fp32' only."""
+        from ..entropy_coding import COST_UNIT, MAP_RECORD_BITS, STEP_MAX, STEP_MIN, check_offsets, check_steps, count_runs, psnr_of_sse
+        self._check_step_arguments("rd_curve", 0, step_offsets=step_offsets)
+        steps = list(range(STEP_MIN, STEP_MAX + 1)) if steps is None else list(steps)
+        steps = check_steps(steps, len(steps))
+        if not steps:
+            raise ValueError("rd_curve: no candidate step")
+        x = self._as_device_images(x)
+        n, H, W = x.shape[0], int(x.shape[1]), int(x.shape[2])
+        codec = self._get_codec()
+        offsets = None if step_offsets is None else check_offsets(step_offsets, n, *codec.latent_shapes(H, W)[4:])
+        with torch.cuda.device(self.device):
+            lat = self.infer_latent_rvs(x)
+            z, y = lat.uq[0].loc.contiguous(), lat.uq[1].loc.contiguous()
+            cost_z, cost_y, sse, _ = codec.rd_ladder(z, y, x, steps, offsets)
+        flushed = float(codec.flushed_bits(H, W))
+        bits = (cost_z[:, None] / float(COST_UNIT) + cost_y / float(COST_UNIT)) + flushed
+        out = dict(steps=steps, bits=bits, bpp=bits / float(H * W), sse=sse, psnr=psnr_of_sse(sse, 3 * H * W),
+                   bits_z=cost_z / float(COST_UNIT), flushed_bits=flushed)
+        if offsets is not None:
+            out["map_bits"] = (MAP_RECORD_BITS * count_runs(offsets)).astype(np.float64)
+        return out
+
+    def _check_step_arguments(self, where, step, target_bpp=None, itinf=None, step_offsets=None, target_psnr=None):
         """The refusals of the quantisation-step arguments that need no image: every one before any launch."""
-        if step is None and target_bpp is None and step_offsets is None:
+        if step is None and target_bpp is None and step_offsets is None and target_psnr is None:
             return
         if self.factorized:
             raise NotImplementedError(f"{where}(step / target_bpp / step_offsets): a factorized-prior model's per-channel tables "
                                       "would have to be rebuilt per step; mean-scale hyperprior models only")
         if step is not None and target_bpp is not None:
             raise ValueError(f"{where}: step and target_bpp exclude each other")
+        if target_psnr is not None and (step is not None or target_bpp is not None):
+            raise ValueError(f"{where}: target_psnr excludes step and target_bpp")
         if itinf is not None:
             raise ValueError(f"{where}: step / target_bpp / step_offsets and itinf exclude each other at the top level (they travel "
                              "inside the itinf dict)")

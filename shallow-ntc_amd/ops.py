@@ -1351,6 +1351,48 @@ def dequant_step_map(symbols, hyper, kmap, lut):
     return y_hat
 
 
+def _ladder_out(y, nsteps, out, where):
+    """The output of the ladder-dequantisation kernels: float32 [nsteps, n, h, w, c], candidate-major (``out``: a caller's)."""
+    shape = (nsteps,) + tuple(y.shape)
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=y.device)
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()
+            and out.device == y.device):
+        raise ValueError(f"{where}: out float32 {shape}, contiguous, on the latents' device")
+    return out
+
+
+def step_ladder_dequant(y, hyper, inv_step, step, out=None):
+    """What ``dequant_step(step_symbols(y, ...))`` gives at EVERY candidate step of a ladder shared by the batch, in one pass
+    over y and mu and without a symbol tensor (csrc/quant_step_ladder.hip): ``inv_step`` / ``step`` float32 [nsteps] on the
+    device (entropy_coding.step_tensors), 1 <= nsteps <= 16 -> y_hat float32 [nsteps, n, h, w, c]; ``y_hat[j]`` is candidate
+    j's batch, and ``y_hat.view(nsteps * n, h, w, c)`` all of them as one decoder batch.  Any c (c % 4 != 0 and unaligned views
+    take the element-wise path)."""
+    n, hw, c, stride = _check_step_inputs(y, hyper, ())
+    if y.dtype != torch.float32 or inv_step.dtype != torch.float32 or step.dtype != torch.float32 or inv_step.dim() != 1 \
+            or tuple(step.shape) != tuple(inv_step.shape) or not (inv_step.is_contiguous() and step.is_contiguous()) \
+            or inv_step.device != y.device or step.device != y.device:
+        raise ValueError("step_ladder_dequant: y float32, inv_step / step float32 [nsteps] on the latents' device")
+    y_hat = _ladder_out(y, inv_step.numel(), out, "step_ladder_dequant")
+    capi.call("sntc_step_ladder_dequant", _ptr(y), _ptr(hyper), n, hw, c, stride, _ptr(inv_step), _ptr(step), inv_step.numel(),
+              _ptr(y_hat), _stream())
+    return y_hat
+
+
+def step_map_ladder_dequant(y, hyper, offsets, lut, bases, out=None):
+    """``step_ladder_dequant`` over a map: candidate j quantises position p at the ladder index clip(bases[j] +
+    offsets[image, p], -32, 32) -- ``dequant_step_map(step_map_symbols(y, ...))`` on that map.  ``offsets`` int8 [n, h, w],
+    ``lut`` = entropy_coding.step_lut, ``bases`` int32 [nsteps] on the device."""
+    n, hw, c, stride = _check_step_inputs(y, hyper, ())
+    _check_step_map(y, offsets, lut, "step_map_ladder_dequant")
+    if y.dtype != torch.float32 or bases.dtype != torch.int32 or bases.dim() != 1 or not bases.is_contiguous() or bases.device != y.device:
+        raise ValueError("step_map_ladder_dequant: y float32, bases int32 [nsteps] on the latents' device")
+    y_hat = _ladder_out(y, bases.numel(), out, "step_map_ladder_dequant")
+    capi.call("sntc_step_map_ladder_dequant", _ptr(y), _ptr(hyper), n, hw, c, stride, _ptr(offsets), _ptr(lut), _ptr(bases),
+              bases.numel(), _ptr(y_hat), _stream())
+    return y_hat
+
+
 # ------------------------------------------------------------------------------------------
 # SGA iterative inference (include/sntc.h "SGA" section)
 # ------------------------------------------------------------------------------------------

@@ -9,7 +9,11 @@ The work units are (lambda, image) pairs; unit u goes to rank u mod N, every ran
 and ONE all-gather of the per-unit (bpp, psnr, mse, rd_loss) rows closes the run (no data-path collective).  Weights:
 the latest checkpoint of a workdir whose run name carries that rd_lambda (--workdirs), otherwise framework-default
 initial values (the curve is then a plumbing check, not a trained R-D curve).  Images: PNG files (--data-glob) or the
-seeded synthetic Kodak-shaped set."""
+seeded synthetic Kodak-shaped set.
+--ladder: per lambda, ALSO the R-D curve of its weights over the whole quantisation-step ladder -- a unit's row is
+``Model.rd_curve(image)`` (one encoder pass, the candidates decoded as batches; the file's bits and the decoded pixels'
+PSNR at every step) and the output gains ``ladder``: per lambda and step the mean file bpp and PSNR.  Mean-scale
+hyperprior configs only.  Without the switch the run and its output are unchanged."""
 import argparse
 import json
 import sys
@@ -37,6 +41,7 @@ ap.add_argument("--workdirs", nargs="*", default=[])
 ap.add_argument("--data-glob", default=None)
 ap.add_argument("--images", type=int, default=24)
 ap.add_argument("--out", default=None)
+ap.add_argument("--ladder", action="store_true", help="add the quantisation-step ladder's R-D curve per lambda (Model.rd_curve)")
 args = ap.parse_args()
 
 rank, local_rank, world = D.init()
@@ -68,14 +73,32 @@ def evaluate_unit(u):
     return [m["bpp"], m["psnr"], m["mse"], m["rd_loss"]]
 
 
+def ladder_unit(u):
+    evaluate_unit(u)                                                  # the unit's model, as the sweep builds it
+    li, ii = units[u]
+    rd = models[li].rd_curve(images[ii][None])
+    return np.concatenate([rd["bpp"][0], rd["psnr"][0]])
+
+
 table = D.run_units(len(units), evaluate_unit, device=dev, width=4)
+if args.ladder:
+    from shallow_ntc_amd.entropy_coding import STEP_MAX, STEP_MIN
+    steps = list(range(STEP_MIN, STEP_MAX + 1))
+    ladder_table = D.run_units(len(units), ladder_unit, device=dev, width=2 * len(steps))
 if rank == 0:
     curve = []
     for li, lam in enumerate(args.lambdas):
         t = table[li * len(images):(li + 1) * len(images)]
         curve.append(dict(rd_lambda=lam, bpp=float(t[:, 0].mean()), psnr=float(t[:, 1].mean()), mse=float(t[:, 2].mean()),
                           rd_loss=float(t[:, 3].mean()), images=len(images), trained=lam in by_lambda))
-    out = json.dumps(dict(config=args.config, n_gpus=world, curve=curve), indent=1)
+    result = dict(config=args.config, n_gpus=world, curve=curve)
+    if args.ladder:
+        result["ladder"] = []
+        for li, lam in enumerate(args.lambdas):
+            t = ladder_table[li * len(images):(li + 1) * len(images)]
+            result["ladder"].append(dict(rd_lambda=lam, steps=steps, file_bpp=t[:, :len(steps)].mean(axis=0).tolist(),
+                                         psnr=t[:, len(steps):].mean(axis=0).tolist()))
+    out = json.dumps(result, indent=1)
     if args.out:
         Path(args.out).write_text(out)
     print(out)
