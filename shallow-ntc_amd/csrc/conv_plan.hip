@@ -769,6 +769,13 @@ static Sched schedule(const sntc_conv_plan* p, const Geo& g, int64_t n, bool fus
     // higher clock for it; 256 x 128 leaves one wave per SIMD and stalls on every barrier
     // (round 3, back-to-back launches: 128 x 96 beats 128 x 128 by 3.5 % on the 320 -> 480 layer whose 480 columns it fits exactly,
     // where the old 0.97 let the stream-K worker count tip the choice the other way)
+    // (the 320-column launch of the 3x3 480 -> 640 layer, device idle, tools/layer_candidates.py, profiles/hs3_candidates.txt --
+    // 18 x 32 x 48: 128 x 64 stream-K on 768 workers 618 us, this model's pick; 128 x 160, two exact column tiles, 432 tiles on 512
+    // slots, 702 us stream-K and 700 us one workgroup per tile; 128 x 128 padded to 384 columns 700 us.  The `resident / workers`
+    // charge above for the 80 idle slots, 512 / 432 = 1.185, puts 128 x 160 at 1.135 x the cost of 128 x 64; the clock says 1.14:
+    // an idle slot IS idle throughput, the factor stays.  6 x 48 x 32: 64 x 64 one workgroup per tile 237 us, this model's pick,
+    // nothing else within 6 %.  A trial build with column-major twins of 128 x 64 / 128 x 160: worth nothing on the 320-column
+    // launch, 618 against 619 us, nothing in the two-stream step, 2 % on the whole layer alone, 1235 against 1259 us -- not built)
     static const double kRate[kNumVariants + 1] = {0, 0.86, 0.93, 1.00, 1.00, 0.97, 0.90, 0.85, 0.90, 1.02, 0.40};
     cost /= kRate[v];
 #ifdef SNTC_DIAG
