@@ -571,7 +571,7 @@ int sntc_step_ladder_cost(const float* y, const float* mu, int n, int64_t hw, in
                           int total_entries, const uint32_t* cost_q, uint64_t* cost, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
- * The same three rules with the ladder index varying per latent POSITION (csrc/quant_step_map.hip; region-of-interest coding,
+ * The same three rules with the ladder index varying per latent POSITION (csrc/quant_step.hip; region-of-interest coding,
  *   wire format 7): kmap int8 [n][hw], one index k in [-32, 32] per position, shared by its c channels.  step / inv_step come
  *   from ONE table the host uploads, lut float [2][65]: lut[k + 32] = float32(r^k), lut[65 + k + 32] = float32(r^-k) (float64,
  *   rounded once; never recomputed on the device).  The kernels clamp every index they read into [-32, 32]: no byte of a map
@@ -593,7 +593,7 @@ int sntc_step_map_ladder_cost(const float* y, const float* mu, int n, int64_t hw
                               int ntables, int total_entries, const uint32_t* cost_q, uint64_t* cost, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
- * The distortion side of the ladder (csrc/quant_step_ladder.hip, DESIGN.md 4.7 "quality target"): what every candidate step
+ * The distortion side of the ladder (csrc/quant_step.hip, DESIGN.md 4.7 "quality target"): what every candidate step
  *   DECODES to, in one pass.  The reference decodes y_hat = round(y - mu) + mu once per evaluation (mshyper/models.py:273-279);
  *   here, per element and candidate j (1 <= nsteps <= 16), with the three rules above and nothing else,
  *     s = (int)rintf((y - mu) * inv_step[j]),  y_hat[j][image][position][channel] = fmaf(step[j], (float)s, mu)

@@ -149,7 +149,7 @@ __global__ void __launch_bounds__(256) sga_normal_bwd_kernel(const float* __rest
 // pixel (V = 4: 16-byte loads and stores, c % 4 == 0 and aligned pointers; V = 1 otherwise).
 // MAP ("SGA on a step map"; the same reference lines, mshyper/models.py:285-291 and
 // common/latent_rvs_utils.py:8-48, with the grid varying per latent position): the triple comes from where the coder's map
-// kernels take it (quant_step_map.hip) -- a unit is V channels of ONE position, so the thread reads one byte of kmap [n][hw],
+// kernels take it (quant_step.hip) -- a unit is V channels of ONE position, so the thread reads one byte of kmap [n][hw],
 // clamps it (map_index) and reads step and inverse step from lut [2][kMapLut]; k is then a per-lane value and nothing is
 // recomputed with expf.  One body for both: the per-image instances read their triple once, before the loop, as before.
 template <int V, bool MAP>

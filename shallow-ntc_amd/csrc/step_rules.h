@@ -1,6 +1,5 @@
 // step_rules.h -- the quantisation-step rule of the scale ladder, one device function per half, shared by the
-// coder's kernels (quant_step.hip per image, quant_step_map.hip per latent position) and by SGA iterative inference at a step
-// (sga.hip):
+// coder's kernels (quant_step.hip, per image and per latent position) and by SGA iterative inference at a step (sga.hip):
 //   symbol    s = (int)rintf((y - mu) * inv_step)            float32 subtract (step_diff), then float32 multiply (step_round)
 //   table id  t = clamp(t0 - k, 0, 63)                       step_table_id
 //   value     y_hat = fmaf(step, (float)s, mu)               step_value
@@ -15,7 +14,7 @@ __device__ __forceinline__ int step_round(float d, float inv_step) { return (int
 
 __device__ __forceinline__ float step_value(int s, float mu, float step) { return fmaf(step, (float)s, mu); }
 
-// The table-id rule of the coder's kernels (quant_step.hip per image, quant_step_map.hip per position): the table `shift`
+// The table-id rule of the coder's kernels (quant_step.hip, per image and per position): the table `shift`
 // places down the ladder; off the ladder's ends the end table stays.
 constexpr int kLadderTop = 63;                              // last table of the scale ladder (64 normal tables)
 
@@ -29,7 +28,7 @@ __device__ __forceinline__ float step_scaled(float d, float inv_step) { return d
 
 __device__ __forceinline__ float step_value_at(float v, float mu, float step) { return fmaf(step, v, mu); }
 
-// A ladder index per latent POSITION (quant_step_map.hip, the SGA map kernels of sga.hip): the host uploads one table `lut`,
+// A ladder index per latent POSITION (quant_step.hip, the SGA map kernels of sga.hip): the host uploads one table `lut`,
 // float32 [2][kMapLut], row 0 = step, row 1 = inv_step, column k - kMapMin; every kernel clamps the byte it reads from a map
 // with map_index before it indexes the table, so a stray byte can never read outside it.
 constexpr int kMapMin = -32, kMapMax = 32;                  // ladder indexes a map may hold

@@ -21,7 +21,7 @@ Wire format v5 = v3 with version byte 5 and, between the header and the length f
   r = exp(SCALE_FACTOR), and coded with the table k places down the ladder (sigma_i / r^k = sigma_(i-k): the same 64 tables serve every
   step; csrc/quant_step.hip).  Written only when some index is non-zero: all zero is the v3 blob, byte for byte.
 Wire format v7 = v3 with version byte 7 and, between the header and the length fields, u32 record count | the records: the ladder
-  index of EVERY latent position (all C channels of a position share it; region-of-interest coding, csrc/quant_step_map.hip) as
+  index of EVERY latent position (all C channels of a position share it; region-of-interest coding, csrc/quant_step.hip) as
   maximal runs in raster order, image after image, a record = i8 index | u16 run length 1 .. 65535 (``pack_runs``); a run never
   crosses an image boundary.  Written only when some image's map really varies: constant maps are the v5 / v3 blob of those
   indexes, byte for byte -- a file has one spelling.  Version 6 is not assigned and stays refused.
@@ -652,33 +652,47 @@ def step_table_ids(base_ids, shift):
     return out
 
 
-def step_ladder_cost(y, hyper, base_ids, steps, tables: DeviceTables, tensors=None):
-    """``rans_cost`` of the symbols and ids ``ops.step_symbols`` would form at EVERY ladder index of ``steps`` (shared by the
-    batch), without forming them: one pass over y / mu / ids per launch of at most ``LADDER_MAX`` candidates.
-    -> int64 [n, len(steps)] on the device, 2^-16 bit.  ``tensors``: ``step_tensors(steps, device)`` if the caller keeps them."""
+def _check_ladder_latents(y, hyper, base_ids, what):
     c = y.shape[-1]
     if y.dtype != torch.float32 or hyper.dtype != torch.float32 or base_ids.dtype != torch.int16 or y.dim() != 4 or hyper.dim() != 4 \
             or tuple(hyper.shape[:3]) != tuple(y.shape[:3]) or hyper.shape[-1] not in (c, 2 * c) or tuple(base_ids.shape) != tuple(y.shape) \
             or not (y.is_contiguous() and hyper.is_contiguous() and base_ids.is_contiguous()):
-        raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_ladder_cost: y float32 [n, h, w, c], hyper [n, h, w, c or 2 c], ids int16 like y, contiguous")
-    steps = check_steps(list(steps), len(steps))
-    if not steps:
-        raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_ladder_cost: no candidate step")
-    n, hw = y.shape[0], y.shape[1] * y.shape[2]
-    _, inv, sh = step_tensors(steps, y.device) if tensors is None else tensors
-    cost = torch.empty((n, len(steps)), dtype=torch.int64, device=y.device)
-    for lo in range(0, len(steps), LADDER_MAX):
-        k = min(LADDER_MAX, len(steps) - lo)
-        part = cost if k == len(steps) else torch.empty((n, k), dtype=torch.int64, device=y.device)
-        capi.call("sntc_step_ladder_cost", _p(y), _p(hyper), n, hw, c, hyper.shape[-1], _p(base_ids), _p(inv[lo:lo + k]), _p(sh[lo:lo + k]),
-                  k, _p(tables.meta), tables.ntables, tables.total, _p(tables.cost_q), _p(part), ops._stream())
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"{what}: y float32 [n, h, w, c], hyper [n, h, w, c or 2 c], ids int16 like y, contiguous")
+
+
+def _ladder_cost_chunks(y, count, launch):
+    """int64 [n, count] on y's device from launches of at most ``LADDER_MAX`` candidates: ``launch(lo, k, part)`` prices candidates
+    lo ... lo + k - 1 into ``part`` int64 [n, k]."""
+    n = y.shape[0]
+    cost = torch.empty((n, count), dtype=torch.int64, device=y.device)
+    for lo in range(0, count, LADDER_MAX):
+        k = min(LADDER_MAX, count - lo)
+        part = cost if k == count else torch.empty((n, k), dtype=torch.int64, device=y.device)
+        launch(lo, k, part)
         if part is not cost:
             cost[:, lo:lo + k] = part
     return cost
 
 
+def step_ladder_cost(y, hyper, base_ids, steps, tables: DeviceTables, tensors=None):
+    """``rans_cost`` of the symbols and ids ``ops.step_symbols`` would form at EVERY ladder index of ``steps`` (shared by the
+    batch), without forming them: one pass over y / mu / ids per launch of at most ``LADDER_MAX`` candidates.
+    -> int64 [n, len(steps)] on the device, 2^-16 bit.  ``tensors``: ``step_tensors(steps, device)`` if the caller keeps them."""
+    _check_ladder_latents(y, hyper, base_ids, "step_ladder_cost")
+    steps = check_steps(list(steps), len(steps))
+    if not steps:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_ladder_cost: no candidate step")
+    n, hw, c = y.shape[0], y.shape[1] * y.shape[2], y.shape[3]
+    _, inv, sh = step_tensors(steps, y.device) if tensors is None else tensors
+
+    def launch(lo, k, part):
+        capi.call("sntc_step_ladder_cost", _p(y), _p(hyper), n, hw, c, hyper.shape[-1], _p(base_ids), _p(inv[lo:lo + k]), _p(sh[lo:lo + k]),
+                  k, _p(tables.meta), tables.ntables, tables.total, _p(tables.cost_q), _p(part), ops._stream())
+    return _ladder_cost_chunks(y, len(steps), launch)
+
+
 def step_lut(device):
-    """What the step-map kernels (csrc/quant_step_map.hip) look steps up in: float32 [2, 65] on ``device``, row 0 =
+    """What the step-map kernels (csrc/quant_step.hip) look steps up in: float32 [2, 65] on ``device``, row 0 =
     step_size(k), row 1 = step_size(-k), column k - STEP_MIN (``step_size``: float64, rounded once)."""
     ks = range(STEP_MIN, STEP_MAX + 1)
     return torch.from_numpy(np.array([[step_size(k) for k in ks], [step_size(-k) for k in ks]], np.float32)).to(device)
@@ -714,30 +728,22 @@ def step_map_ladder_cost(y, hyper, base_ids, offsets, bases, tables: DeviceTable
     STEP_MIN, STEP_MAX); ``offsets`` int8 [n, h, w] on the device, ``bases`` ladder indexes shared by the batch.
     -> int64 [n, len(bases)] on the device, 2^-16 bit.  ``lut``: ``step_lut(device)``, ``bases_d``: ``bases`` as int32 on the device,
     if the caller keeps them (else one small upload each)."""
-    c = y.shape[-1]
-    if y.dtype != torch.float32 or hyper.dtype != torch.float32 or base_ids.dtype != torch.int16 or y.dim() != 4 or hyper.dim() != 4 \
-            or tuple(hyper.shape[:3]) != tuple(y.shape[:3]) or hyper.shape[-1] not in (c, 2 * c) or tuple(base_ids.shape) != tuple(y.shape) \
-            or not (y.is_contiguous() and hyper.is_contiguous() and base_ids.is_contiguous()):
-        raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_map_ladder_cost: y float32 [n, h, w, c], hyper [n, h, w, c or 2 c], ids int16 like y, contiguous")
+    _check_ladder_latents(y, hyper, base_ids, "step_map_ladder_cost")
     _check_map(offsets, y, "step_map_ladder_cost")
     bases = check_steps(list(bases), len(bases))
     if not bases:
         raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_map_ladder_cost: no candidate step")
     lut = step_lut(y.device) if lut is None else lut
     _check_lut(lut, y, "step_map_ladder_cost")
-    n, hw = y.shape[0], y.shape[1] * y.shape[2]
+    n, hw, c = y.shape[0], y.shape[1] * y.shape[2], y.shape[3]
     base_d = torch.tensor(bases, dtype=torch.int32).to(y.device) if bases_d is None else bases_d
     if base_d.dtype != torch.int32 or tuple(base_d.shape) != (len(bases),) or not base_d.is_contiguous() or base_d.device != y.device:
         raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_map_ladder_cost: bases_d = the candidates as int32 on the latents' device")
-    cost = torch.empty((n, len(bases)), dtype=torch.int64, device=y.device)
-    for lo in range(0, len(bases), LADDER_MAX):
-        k = min(LADDER_MAX, len(bases) - lo)
-        part = cost if k == len(bases) else torch.empty((n, k), dtype=torch.int64, device=y.device)
+
+    def launch(lo, k, part):
         capi.call("sntc_step_map_ladder_cost", _p(y), _p(hyper), n, hw, c, hyper.shape[-1], _p(base_ids), _p(offsets), _p(lut),
                   _p(base_d[lo:lo + k]), k, _p(tables.meta), tables.ntables, tables.total, _p(tables.cost_q), _p(part), ops._stream())
-        if part is not cost:
-            cost[:, lo:lo + k] = part
-    return cost
+    return _ladder_cost_chunks(y, len(bases), launch)
 
 
 def channel_table_ids(shape, device):
@@ -930,7 +936,7 @@ class Codec:
     def _quant(self, step, step_offsets, n, H, W):
         """``step`` / ``step_offsets`` of the public entry points -> (steps, kmap): (None, None) = today's path; (the n ladder
         indexes, None) where every image's map K = clip(step_i + step_offsets[i], STEP_MIN, STEP_MAX) is constant (the per-image
-        kernels, wire format 5); else (None, K int8 [n, h, w]) (csrc/quant_step_map.hip, wire format 7).  Every refusal here:
+        kernels, wire format 5); else (None, K int8 [n, h, w]) (csrc/quant_step.hip, wire format 7).  Every refusal here:
         before anything is enqueued."""
         if step_offsets is None:
             return self._steps(step, n), None
@@ -964,7 +970,7 @@ class Codec:
     def _symbols(self, z, y, steps=None, pre=None, kmap=None):
         """(z_loc, y_loc) -> what the file carries: (zi int32, z's table ids, y symbols int32, y's table ids, hyper).
         ``steps``: None, or one ladder index per image (csrc/quant_step.hip); ``kmap``: None, or one per position, int8
-        [n, h, w] on the device (csrc/quant_step_map.hip); ``pre``: ``_hyper_of(z)`` if the caller has it."""
+        [n, h, w] on the device (csrc/quant_step.hip); ``pre``: ``_hyper_of(z)`` if the caller has it."""
         m = self.m
         zi, hyper = self._hyper_of(z) if pre is None else pre
         ztid = channel_table_ids(z.shape, m.device)
@@ -1058,7 +1064,7 @@ class Codec:
         int64 [n], cost_y int64 [n, len(steps)]) in 2^-16 bit on the device, no host synchronisation.  y, mu and the scale
         indexes are read once per launch of at most ``LADDER_MAX`` candidates (csrc/quant_step.hip).  ``step_offsets`` (integers
         [n, h, w]): candidate j prices position p at clip(steps[j] + step_offsets[i, p]) -- what ``latents_cost(step=steps[j],
-        step_offsets=...)`` returns (csrc/quant_step_map.hip)."""
+        step_offsets=...)`` returns (csrc/quant_step.hip)."""
         steps = check_steps(list(steps), len(steps))
         if not steps:
             raise ValueError("ladder_cost: no candidate step")
@@ -1074,7 +1080,7 @@ class Codec:
         synchronisation; column j is what ``latents_cost(z_loc, y_loc, x, step=steps[j], step_offsets=...)`` returns, exactly
         (decoding is batch-invariant and the step rule is one header: the decoded SSE of a candidate is a well-defined integer).
         The hyper-synthesis runs once; the candidates go through in chunks of min(LADDER_MAX, max(1, ``chunk_bytes`` // the
-        bytes of one candidate's y_hat)): per chunk ONE launch of csrc/quant_step_ladder.hip writes the dequantised latents of
+        bytes of one candidate's y_hat)): per chunk ONE launch of csrc/quant_step.hip writes the dequantised latents of
         its candidates, candidate-major, and ONE decoder batch of chunk n latents decodes them against the images repeated on
         the device.  ``chunk_bytes`` bounds memory only: the result does not depend on it.  ``pre``: ``_hyper_of(z_loc)`` if
         the caller has it."""

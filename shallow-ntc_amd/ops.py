@@ -1327,7 +1327,7 @@ def _check_step_map(a, kmap, lut, where):
 
 
 def step_map_symbols(y, hyper, base_ids, kmap, lut):
-    """``step_symbols`` with one ladder index per latent POSITION (csrc/quant_step_map.hip): at index k = kmap[image, position]
+    """``step_symbols`` with one ladder index per latent POSITION (csrc/quant_step.hip): at index k = kmap[image, position]
     symbols = rint((y - mu) * lut[1, k + 32]), table ids = clamp(base_ids - k, 0, 63) for all c channels of the position."""
     n, hw, c, stride = _check_step_inputs(y, hyper, ())
     _check_step_map(y, kmap, lut, "step_map_symbols")
@@ -1364,7 +1364,7 @@ def _ladder_out(y, nsteps, out, where):
 
 def step_ladder_dequant(y, hyper, inv_step, step, out=None):
     """What ``dequant_step(step_symbols(y, ...))`` gives at EVERY candidate step of a ladder shared by the batch, in one pass
-    over y and mu and without a symbol tensor (csrc/quant_step_ladder.hip): ``inv_step`` / ``step`` float32 [nsteps] on the
+    over y and mu and without a symbol tensor (csrc/quant_step.hip): ``inv_step`` / ``step`` float32 [nsteps] on the
     device (entropy_coding.step_tensors), 1 <= nsteps <= 16 -> y_hat float32 [nsteps, n, h, w, c]; ``y_hat[j]`` is candidate
     j's batch, and ``y_hat.view(nsteps * n, h, w, c)`` all of them as one decoder batch.  Any c (c % 4 != 0 and unaligned views
     take the element-wise path)."""

@@ -1,5 +1,5 @@
 """Quality-targeted compress (-m gpu; DESIGN.md 4.7, "quality target"): the ladder-dequantisation kernels of
-csrc/quant_step_ladder.hip against the float32 rule in NumPy (bit equality) and against the per-step kernels, ``ladder_distortion``
+csrc/quant_step.hip against the float32 rule in NumPy (bit equality) and against the per-step kernels, ``ladder_distortion``
 against ``coded_cost`` (integer equality), ``rd_curve``, and ``compress(x, target_psnr=...)`` against ``compress(x, step=...)``
 (byte equality) and a brute-force restatement of the rule."""
 from fractions import Fraction

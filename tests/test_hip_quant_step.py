@@ -220,8 +220,13 @@ def test_ladder_cost_is_the_numpy_sum(E, c, stride, dev, normal):
             assert got[:, j].tolist() == seen[k].tolist(), k
 
 
+def offset_view(t, pad, dev):
+    return torch.cat([torch.zeros(pad, dtype=t.dtype, device=dev), t.flatten()])[pad:].view(t.shape)
+
+
 def test_ladder_cost_with_tables_beyond_the_lds_limit(dev):
-    """Descriptors and costs read from global memory (84 tables; the ladder is their first 64): the same exact sums."""
+    """Descriptors and costs read from global memory (84 tables; the ladder is their first 64): the same exact sums, from
+    aligned tensors and from views 4 bytes into their allocation (the element-wise load path)."""
     from shallow_ntc_amd import entropy_coding as ec
     big = big_table_set()
     db, q = ec.DeviceTables(big, dev), ref_cost_table(big)
@@ -230,9 +235,14 @@ def test_ladder_cost_with_tables_beyond_the_lds_limit(dev):
         cs = case_of(*key)
         y, hyper, ids = dev_case(cs, dev)
         got = ec.step_ladder_cost(y, hyper, ids, ladder, db).cpu().numpy()
+        y2, h2, i2 = offset_view(y, 1, dev), offset_view(hyper, 1, dev), offset_view(ids, 2, dev)
+        assert y2.data_ptr() % 16 == 4 and h2.data_ptr() % 16 == 4 and i2.data_ptr() % 8 == 4
+        got2 = ec.step_ladder_cost(y2, h2, i2, ladder, db).cpu().numpy()           # the element-wise load path, tables in memory
         for j, k in enumerate(ladder):
             sym, tid, _ = np_step_symbols(cs["y"], cs["mu"], cs["ids"], [k] * N)
-            assert got[:, j].tolist() == np_cost(sym.reshape(N, -1), tid.reshape(N, -1), big, q).tolist(), k
+            want = np_cost(sym.reshape(N, -1), tid.reshape(N, -1), big, q).tolist()
+            assert got[:, j].tolist() == want, k
+            assert got2[:, j].tolist() == want, k
 
 
 def test_ladder_cost_from_an_offset_view(dev, normal):
@@ -245,8 +255,7 @@ def test_ladder_cost_from_an_offset_view(dev, normal):
         cs = case_of(*key)
         y, hyper, ids = dev_case(cs, dev)
         want = ec.step_ladder_cost(y, hyper, ids, ladder, dt)
-        off = lambda t, pad: torch.cat([torch.zeros(pad, dtype=t.dtype, device=dev), t.flatten()])[pad:].view(t.shape)
-        y2, h2, i2 = off(y, 1), off(hyper, 1), off(ids, 2)
+        y2, h2, i2 = offset_view(y, 1, dev), offset_view(hyper, 1, dev), offset_view(ids, 2, dev)
         assert y2.data_ptr() % 16 == 4 and h2.data_ptr() % 16 == 4 and i2.data_ptr() % 8 == 4
         for a, b, cc in ((y2, h2, i2), (y2, hyper, ids), (y, h2, ids), (y, hyper, i2)):
             assert torch.equal(ec.step_ladder_cost(a, b, cc, ladder, dt), want)

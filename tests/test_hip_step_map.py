@@ -1,6 +1,6 @@
 """Region-of-interest coding (-m gpu; DESIGN.md 4.7, "variable rate"): the per-position quantisation-step kernels of
-csrc/quant_step_map.hip against their NumPy restatement (integer / bit equality) and against the per-image kernels of
-csrc/quant_step.hip, the map ladder cost against ``np_cost``, wire format v7 through compress / decompress, rate control over a map
+csrc/quant_step.hip against their NumPy restatement (integer / bit equality) and against the per-image instances of the same
+kernels, the map ladder cost against ``np_cost``, wire format v7 through compress / decompress, rate control over a map
 and the refusals."""
 from fractions import Fraction
 
@@ -11,7 +11,8 @@ import torch
 
 from test_hip_itinf_bitstream import (big_table_set, fact_model, flushed_bits, hyper_model, image_words, images,  # noqa: F401
                                       payload_bits, slack_bar)
-from test_hip_quant_step import LADDERS, N, STEPS, STRIDE_CASES, case_of, dev_case, dv, latents, normal, round_f32, sse_of  # noqa: F401
+from test_hip_quant_step import (LADDERS, N, STEPS, STRIDE_CASES, case_of, dev_case, dv, latents, normal, offset_view,  # noqa: F401
+                                 round_f32, sse_of)
 from test_rans_cost_host import np_cost, ref_cost_table
 
 pytestmark = pytest.mark.gpu
@@ -151,10 +152,6 @@ def np_ladder(y, mu, ids, offsets, bases, tabs, q):
     return np.stack(cols, axis=1)
 
 
-def offset_view(t, pad, dev):
-    return torch.cat([torch.zeros(pad, dtype=t.dtype, device=dev), t.flatten()])[pad:].view(t.shape)
-
-
 @pytest.mark.parametrize("E,c,stride", CASES, ids=IDS)
 def test_map_ladder_cost_is_the_numpy_sum(E, c, stride, dev, lut, normal):
     """Every [image, candidate] entry = np_cost of the NumPy symbols at clip(base + offsets), for 1, 5 and 16 candidates, with
@@ -178,7 +175,8 @@ def test_map_ladder_cost_is_the_numpy_sum(E, c, stride, dev, lut, normal):
 
 
 def test_map_ladder_cost_with_tables_beyond_the_lds_limit(dev, lut):
-    """Descriptors and costs read from global memory (84 tables; the ladder is their first 64): the same exact sums."""
+    """Descriptors and costs read from global memory (84 tables; the ladder is their first 64): the same exact sums, from
+    aligned tensors and from views 4 bytes into their allocation (the element-wise load path; the map 1 byte into its own)."""
     from shallow_ntc_amd import entropy_coding as ec
     big = big_table_set()
     db, q = ec.DeviceTables(big, dev), ref_cost_table(big)
@@ -186,8 +184,12 @@ def test_map_ladder_cost_with_tables_beyond_the_lds_limit(dev, lut):
         cs = case_of(*key)
         y, hyper, ids = dev_case(cs, dev)
         off = make_map("random", cs, -64, 64, pin=False)
-        got = ec.step_map_ladder_cost(y, hyper, ids, dmap(off, dev), BASES[2], db, lut).cpu().numpy()
-        np.testing.assert_array_equal(got, np_ladder(cs["y"], cs["mu"], cs["ids"], off, BASES[2], big, q))
+        od = dmap(off, dev)
+        want = np_ladder(cs["y"], cs["mu"], cs["ids"], off, BASES[2], big, q)
+        np.testing.assert_array_equal(ec.step_map_ladder_cost(y, hyper, ids, od, BASES[2], db, lut).cpu().numpy(), want)
+        y2, h2, i2, o2 = offset_view(y, 1, dev), offset_view(hyper, 1, dev), offset_view(ids, 2, dev), offset_view(od, 1, dev)
+        assert y2.data_ptr() % 16 == 4 and h2.data_ptr() % 16 == 4 and i2.data_ptr() % 8 == 4 and o2.data_ptr() % 2 == 1
+        np.testing.assert_array_equal(ec.step_map_ladder_cost(y2, h2, i2, o2, BASES[2], db, lut).cpu().numpy(), want)
 
 
 def test_map_ladder_cost_from_an_offset_view(dev, lut, normal):

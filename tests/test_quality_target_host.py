@@ -20,11 +20,15 @@ def test_entry_points_declared_bound_and_built():
         assert re.search(rf"\bint {name}\(", header), f"{name} is not declared in include/sntc.h"
         assert name in _capi.SIGNATURES and hasattr(lib, name)
         assert _capi.SIGNATURES[name][1][-1] is _capi.C.c_void_p          # the stream comes last
-    assert "quant_step_ladder.hip" in (ROOT / "shallow-ntc_amd" / "csrc" / "Makefile").read_text()
-    text = (ROOT / "shallow-ntc_amd" / "csrc" / "quant_step_ladder.hip").read_text()
+    assert "quant_step.hip" in (ROOT / "shallow-ntc_amd" / "csrc" / "Makefile").read_text()
+    text = (ROOT / "shallow-ntc_amd" / "csrc" / "quant_step.hip").read_text()
+    code = "\n".join(line.split("//")[0] for line in text.splitlines())
     # one copy of the step rule, and the shape the kernel promises: no atomics, no LDS
-    assert '#include "step_rules.h"' in text and "float step_diff(" not in text and "rintf" not in text and "fmaf" not in text
-    assert "atomic" not in text.split("namespace sntc")[1] and "__shared__" not in text
+    assert '#include "step_rules.h"' in code and "float step_diff(" not in code and "rintf" not in code and "fmaf" not in code
+    kernel = code.split("void __launch_bounds__(kDequantLadderThreads) step_ladder_dequant_kernel(")
+    assert len(kernel) == 2                                      # one body for the per-image and the map candidates
+    body = kernel[1].split("\n}\n")[0]
+    assert "step_value(step_round(" in body and "atomic" not in body and "__shared__" not in body and "__syncthreads" not in body
 
 
 def test_select_quality_takes_the_cheapest_candidate_that_qualifies():

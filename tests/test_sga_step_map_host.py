@@ -29,7 +29,7 @@ def test_entry_points_declared_bound_and_exported():
     # one copy of the map's clamp and table layout: the header, read by the coder's map kernels and by the SGA ones
     rules = (ROOT / "shallow-ntc_amd" / "csrc" / "step_rules.h").read_text()
     assert "int map_index(" in rules
-    for src in ("quant_step_map.hip", "sga.hip"):
+    for src in ("quant_step.hip", "sga.hip"):
         text = (ROOT / "shallow-ntc_amd" / "csrc" / src).read_text()
         assert '#include "step_rules.h"' in text and "int map_index(" not in text and "map_index(" in text
 

@@ -3,7 +3,7 @@
 real-vs-estimated rate.  python tools/profile_bitstream.py [--batch 18] [--hw 512 768] [--segments 2]
 
     python tools/profile_bitstream.py --step-map profiles/step_map.json [--reps 25]      (at least 25 repetitions)
-measures region-of-interest coding instead (csrc/quant_step_map.hip, DESIGN.md 4.7 "variable rate") and writes the JSON:
+measures region-of-interest coding instead (csrc/quant_step.hip, DESIGN.md 4.7 "variable rate") and writes the JSON:
   * ``sntc_step_map_ladder_cost`` at 16 candidates against ``sntc_step_ladder_cost`` at the same 16, on the latents of an
     18 x 512 x 768 batch at C = 320 (those of tools/profile_quant_step.py), with offsets 0 on a centred rectangle and +12 around
     it, and with offsets all 0 (the same integers as the uniform launch: asserted);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Quality-targeted compress (csrc/quant_step_ladder.hip, DESIGN.md 4.7 "quality target"): what the ladder-dequantisation launch
+"""Quality-targeted compress (csrc/quant_step.hip, DESIGN.md 4.7 "quality target"): what the ladder-dequantisation launch
 is bound by, what decoding the candidates as batches buys over one ``coded_cost`` per step, and what
 ``compress(target_psnr=...)`` costs beside ``compress(target_bpp=...)``.
 
