@@ -675,7 +675,7 @@ def _ladder_cost_chunks(y, count, launch):
 
 
 def step_ladder_cost(y, hyper, base_ids, steps, tables: DeviceTables, tensors=None):
-    """``rans_cost`` of the symbols and ids ``ops.step_symbols`` would form at EVERY ladder index of ``steps`` (shared by the
+    """``rans_cost`` of the symbols and ids an image ``StepGrid`` would form at EVERY ladder index of ``steps`` (shared by the
     batch), without forming them: one pass over y / mu / ids per launch of at most ``LADDER_MAX`` candidates.
     -> int64 [n, len(steps)] on the device, 2^-16 bit.  ``tensors``: ``step_tensors(steps, device)`` if the caller keeps them."""
     _check_ladder_latents(y, hyper, base_ids, "step_ladder_cost")
@@ -696,6 +696,119 @@ def step_lut(device):
     step_size(k), row 1 = step_size(-k), column k - STEP_MIN (``step_size``: float64, rounded once)."""
     ks = range(STEP_MIN, STEP_MAX + 1)
     return torch.from_numpy(np.array([[step_size(k) for k in ks], [step_size(-k) for k in ks]], np.float32)).to(device)
+
+
+def require_fp32(precision, what):
+    """The refusal every quantisation-step entry point shares, raised before anything is enqueued."""
+    if precision != "fp32":
+        raise NotImplementedError(f"{what} runs in precision 'fp32', not {precision!r}: the pre-split dequantisation is not extended")
+
+
+class StepGrid:
+    """How y - mu of a batch of n images is quantised (csrc/quant_step.hip): ``kind`` "unit" (step 1, wire format
+    3), "image" (``steps``: one ladder index per image, format 5) or "map" (``kmap``: the absolute index of every latent position,
+    int8 [n, h, w], format 7).  Host state; what the kernels read goes up on first use (``on``) and stays with the object.  Every
+    operation picks its kernel here, once."""
+
+    def __init__(self, kind, n=None, steps=None, kmap=None):
+        self.kind, self.n, self.steps, self.kmap, self._on = kind, n, steps, kmap, None
+
+    @classmethod
+    def image(cls, steps):
+        """One ladder index per image, on the per-image kernels even where every index is 0 (a per-image ``rd_lambda``)."""
+        return cls("image", len(steps), steps=[int(k) for k in steps])
+
+    @classmethod
+    def resolve(cls, step, step_offsets, n, h=None, w=None):
+        """``step`` / ``step_offsets`` of the public entry points -> the grid of K = clip(step_i + step_offsets[i], STEP_MIN,
+        STEP_MAX): unit where every index is 0 (or nothing is given), image where every image's K is constant, else map.
+        ValueError on what ``check_steps`` / ``check_offsets`` refuse.  (h, w): the latent resolution, read with offsets only."""
+        offs = None if step_offsets is None else check_offsets(step_offsets, n, h, w)
+        ks = check_steps(0 if step is None else step, n)
+        if offs is not None:
+            kmap = index_map(ks, offs)
+            ks = uniform_steps(kmap)
+            if ks is None:
+                return cls("map", n, kmap=kmap)
+        return cls.image(ks) if any(ks) else cls("unit", n)
+
+    @classmethod
+    def from_header(cls, hd):
+        """The grid a parsed header (``parse_v3`` / ``parse_v7``) announces."""
+        if hd.get("kmap") is not None:
+            return cls("map", hd["n"], kmap=hd["kmap"])
+        return cls("unit", hd["n"]) if hd["steps"] is None else cls.image(hd["steps"])
+
+    def on(self, device):
+        """What the kernels read, on ``device`` (one small upload, kept): image -> ``step_tensors`` = (step, inv_step, shift);
+        map -> (kmap int8 [n, h, w], ``cached_step_lut``); unit -> ()."""
+        device = torch.device(device)
+        if self._on is None or self._on[0] != device:
+            t = () if self.kind == "unit" else tuple(step_tensors(self.steps, device)) if self.kind == "image" else \
+                (torch.from_numpy(self.kmap).to(device), cached_step_lut(device))
+            self._on = (device, t)
+        return self._on[1]
+
+    def symbols(self, y, hyper):
+        """-> (y's symbols int32, their table ids)."""
+        if self.kind == "unit":
+            sym = ops.entropy_scale_normal(y, hyper, want_symbols=True)[2]
+            return sym, scale_table_ids(hyper)
+        t = self.on(y.device)
+        if self.kind == "image":
+            return ops.step_symbols(y, hyper, scale_table_ids(hyper), t[1], t[2])
+        return ops.step_map_symbols(y, hyper, scale_table_ids(hyper), *t)
+
+    def table_ids(self, base_ids):
+        """The decoder's table ids from ``scale_table_ids``: the tables K places down the ladder, its start tables unchanged."""
+        if self.kind == "unit":
+            return base_ids
+        t = self.on(base_ids.device)
+        return step_table_ids(base_ids, t[2]) if self.kind == "image" else step_map_table_ids(base_ids, t[0])
+
+    def dequant(self, sym, hyper, s3=False):
+        """y_hat = mu + step * symbols.  ``s3`` (unit only): the synthesis takes y_hat pre-split (``takes_s3``)."""
+        if self.kind == "unit":
+            return ops.dequant_split3(sym, hyper) if s3 else ops.dequant_scale_normal(sym, hyper)
+        t = self.on(sym.device)
+        return ops.dequant_step(sym, hyper, t[0]) if self.kind == "image" else ops.dequant_step_map(sym, hyper, *t)
+
+    def sga_fwd(self, y_loc, hyper, tau, noise, seed, step):
+        if self.kind == "unit":
+            return ops.sga_normal_fwd(y_loc, hyper, tau, noise, seed, step)
+        t = self.on(y_loc.device)
+        if self.kind == "image":
+            return ops.sga_normal_step_fwd(y_loc, hyper, tau, t, noise, seed, step)
+        return ops.sga_normal_step_map_fwd(y_loc, hyper, tau, *t, noise, seed, step)
+
+    def sga_bwd(self, g_yt, sp, dv, dr, weight, dweight=None):
+        """``dweight`` float32 [n] on the device (image only): what multiplies each image's distortion gradient."""
+        if self.kind == "unit":
+            return ops.sga_normal_bwd(g_yt, sp, dv, dr, weight)
+        t = self.on(g_yt.device)
+        if self.kind == "image":
+            return ops.sga_normal_step_bwd(g_yt, sp, dv, dr, weight, t + (dweight,))
+        return ops.sga_normal_step_map_bwd(g_yt, sp, dv, dr, weight, *t)
+
+    def pack(self, *fields) -> bytes:
+        """Everything of the blob in front of the payload; ``fields``: ``pack_v3``'s, up to the stream lengths."""
+        return pack_v7(*fields, self.kmap) if self.kind == "map" else pack_v3(*fields, self.steps)
+
+    def position_weights(self, h=None, w=None):
+        """omega of ``coded_cost(weighted=True)``, float64 [n, h, w]: ``position_weights`` of the map; a unit or image grid
+        broadcasts its indexes over the (h, w) positions it is given."""
+        if self.kind == "map":
+            return position_weights(self.kmap)
+        return position_weights(index_map(self.steps or [0] * self.n, np.zeros((self.n, h, w), np.int8)))
+
+
+_step_luts = {}
+
+
+def cached_step_lut(device):
+    """``step_lut`` on ``device``, uploaded once."""
+    device = torch.device(device)
+    return _step_luts[device] if device in _step_luts else _step_luts.setdefault(device, step_lut(device))
 
 
 def _check_map(kmap, like, what):
@@ -919,81 +1032,40 @@ class Codec:
                                  f"{H} x {W}: {(n, hz, wz, cz)} / {(n, h, w, c)}")
         return n, H, W
 
-    def _steps(self, step, n):
-        """``step`` of the public entry points -> None (today's path: step 1 for every image) or the n ladder indexes."""
-        if step is None:
-            return None
-        ks = check_steps(step, n)
-        if self.m._precision != "fp32":
-            raise NotImplementedError(f"quantisation steps run in precision 'fp32', not {self.m._precision!r}: the pre-split "
-                                      "dequantisation is not extended")
-        return ks if any(ks) else None
-
-    def _step_tensors(self, steps):
-        """``step_tensors`` of ladder indexes on the model's device (one small upload, on the current stream)."""
-        return step_tensors(steps, self.m.device)
-
-    def _quant(self, step, step_offsets, n, H, W):
-        """``step`` / ``step_offsets`` of the public entry points -> (steps, kmap): (None, None) = today's path; (the n ladder
-        indexes, None) where every image's map K = clip(step_i + step_offsets[i], STEP_MIN, STEP_MAX) is constant (the per-image
-        kernels, wire format 5); else (None, K int8 [n, h, w]) (csrc/quant_step.hip, wire format 7).  Every refusal here:
-        before anything is enqueued."""
-        if step_offsets is None:
-            return self._steps(step, n), None
-        c, cz, hz, wz, h, w = self.latent_shapes(H, W)
-        offs = check_offsets(step_offsets, n, h, w)
-        ks = check_steps(0 if step is None else step, n)
-        if self.m._precision != "fp32":
-            raise NotImplementedError(f"quantisation steps run in precision 'fp32', not {self.m._precision!r}: the pre-split "
-                                      "dequantisation is not extended")
-        kmap = index_map(ks, offs)
-        ks = uniform_steps(kmap)
-        if ks is not None:
-            return (ks if any(ks) else None), None
-        return None, kmap
-
-    def _map_lut(self):
-        """``step_lut`` on the model's device, uploaded once."""
-        if getattr(self, "_lut", None) is None:
-            self._lut = step_lut(self.m.device)
-        return self._lut
-
-    def _map_tensor(self, kmap):
-        """A host map (absolute indexes or offsets, int8 [n, h, w]) on the model's device: one small upload."""
-        return torch.from_numpy(kmap).to(self.m.device)
+    def _grid(self, step, step_offsets, n, H, W):
+        """``step`` / ``step_offsets`` of the public entry points -> their ``StepGrid`` (``StepGrid.resolve`` at this model's latent
+        resolution).  Every refusal here: before anything is enqueued."""
+        h, w = (None, None) if step_offsets is None else self.latent_shapes(H, W)[4:]
+        grid = StepGrid.resolve(step, step_offsets, n, h, w)
+        if step is not None or step_offsets is not None:
+            require_fp32(self.m._precision, "a quantisation step")
+        return grid
 
     def _hyper_of(self, z):
         """z_loc -> (zi int32, the hyper-synthesis of it): what every step shares."""
         zi = round_to_int(z)
         return zi, self.m._hyper_synthesis(int_to_float(zi))
 
-    def _symbols(self, z, y, steps=None, pre=None, kmap=None):
+    def _symbols(self, z, y, grid, pre=None):
         """(z_loc, y_loc) -> what the file carries: (zi int32, z's table ids, y symbols int32, y's table ids, hyper).
-        ``steps``: None, or one ladder index per image (csrc/quant_step.hip); ``kmap``: None, or one per position, int8
-        [n, h, w] on the device (csrc/quant_step.hip); ``pre``: ``_hyper_of(z)`` if the caller has it."""
+        ``grid``: the ``StepGrid`` y - mu is quantised on; ``pre``: ``_hyper_of(z)`` if the caller has it."""
         m = self.m
+        grid.on(m.device)                                          # its upload, if any, before anything is enqueued
         zi, hyper = self._hyper_of(z) if pre is None else pre
         ztid = channel_table_ids(z.shape, m.device)
-        if kmap is not None:
-            sym, ytid = ops.step_map_symbols(y, hyper, scale_table_ids(hyper), kmap, self._map_lut())
-            return zi, ztid, sym, ytid, hyper
-        if steps is None:
-            _, _, sym = ops.entropy_scale_normal(y, hyper, want_symbols=True)
-            return zi, ztid, sym, scale_table_ids(hyper), hyper
-        _, inv, sh = self._step_tensors(steps)
-        sym, ytid = ops.step_symbols(y, hyper, scale_table_ids(hyper), inv, sh)
+        sym, ytid = grid.symbols(y, hyper)
         return zi, ztid, sym, ytid, hyper
 
-    def _launch_latents(self, z, y, image_hw, steps=None, pre=None, kmap=None):
-        """The device half of ``compress_latents`` on the current stream, no host synchronisation.  ``kmap``: the host map of
-        ``_quant`` (it travels in the file)."""
+    def _launch_latents(self, z, y, image_hw, grid, pre=None):
+        """The device half of ``compress_latents`` on the current stream, no host synchronisation.  ``grid`` travels in the
+        file."""
         n, H, W = self._check_latents(z, y, image_hw)
-        zi, ztid, sym, ytid, _ = self._symbols(z, y, steps, pre, None if kmap is None else self._map_tensor(kmap))
+        zi, ztid, sym, ytid, _ = self._symbols(z, y, grid, pre)
         sz, sy = _segments(zi[0].numel()), _segments(sym[0].numel())
         lz, ly = _lanes(-(-zi[0].numel() // sz)), _lanes(-(-sym[0].numel() // sy))
         zs, zlen = rans_encode_launch(zi, ztid, self.z_tables, sz, lz)
         ys, ylen = rans_encode_launch(sym, ytid, self.y_tables, sy, ly)
-        return dict(n=n, H=H, W=W, z=z, y=y, sz=sz, sy=sy, lz=lz, ly=ly, zs=zs, zlen=zlen, ys=ys, ylen=ylen, steps=steps, kmap=kmap)
+        return dict(n=n, H=H, W=W, z=z, y=y, sz=sz, sy=sy, lz=lz, ly=ly, zs=zs, zlen=zlen, ys=ys, ylen=ylen, grid=grid)
 
     def _finish(self, jobs):
         """Launched jobs -> their blobs: the stream lengths of ALL jobs come back in one copy, the packed payloads in another."""
@@ -1013,8 +1085,7 @@ class Codec:
             zw, yw = int(j["zl"].sum()), int(j["yl"].sum())
             dims = (y.shape[-1], z.shape[-1], z.shape[1], z.shape[2], y.shape[1], y.shape[2])
             fields = (ARITH[m._precision], j["n"], j["H"], j["W"], dims, j["sz"], j["sy"], j["lz"], j["ly"], j["zl"], j["yl"])
-            head = pack_v3(*fields, j.get("steps")) if j.get("kmap") is None else pack_v7(*fields, j["kmap"])
-            out.append(head + words[o:o + zw + yw].tobytes())
+            out.append(j["grid"].pack(*fields) + words[o:o + zw + yw].tobytes())
             o += zw + yw
         return out
 
@@ -1027,9 +1098,9 @@ class Codec:
         resolution, added to the image's step per position and clipped to the ladder (wire format 7 where the result varies
         inside an image; a constant result is the v5 / v3 blob of those indexes, byte for byte)."""
         m = self.m
-        steps, kmap = self._quant(step, step_offsets, z_loc.shape[0], int(image_hw[0]), int(image_hw[1]))
+        grid = self._grid(step, step_offsets, z_loc.shape[0], int(image_hw[0]), int(image_hw[1]))
         with torch.cuda.device(m.device):
-            return self._finish([self._launch_latents(z_loc.contiguous(), y_loc.contiguous(), image_hw, steps, kmap=kmap)])[0]
+            return self._finish([self._launch_latents(z_loc.contiguous(), y_loc.contiguous(), image_hw, grid)])[0]
 
     def latents_cost(self, z_loc, y_loc, x, step=None, step_offsets=None):
         """What ``compress_latents`` would write for these latents and what ``decompress`` would make of it, without writing it:
@@ -1037,26 +1108,22 @@ class Codec:
         device, no host synchronisation.  ``step`` / ``step_offsets`` as in ``compress_latents``."""
         m = self.m
         n, H, W = self._check_latents(z_loc, y_loc, x.shape[1:3])
-        steps, kmap = self._quant(step, step_offsets, n, H, W)
-        kmap = None if kmap is None else self._map_tensor(kmap)
-        zi, ztid, sym, ytid, hyper = self._symbols(z_loc.contiguous(), y_loc.contiguous(), steps, kmap=kmap)
+        grid = self._grid(step, step_offsets, n, H, W)
+        zi, ztid, sym, ytid, hyper = self._symbols(z_loc.contiguous(), y_loc.contiguous(), grid)
         cost_z, cost_y = rans_cost(zi, ztid, self.z_tables), rans_cost(sym, ytid, self.y_tables)
-        if kmap is not None:
-            y_hat = ops.dequant_step_map(sym, hyper, kmap, self._map_lut())
-        elif steps is not None:
-            y_hat = ops.dequant_step(sym, hyper, self._step_tensors(steps)[0])
-        else:
-            y_hat = ops.dequant_split3(sym, hyper) if m._synthesis.takes_s3(sym.shape[1], sym.shape[2]) else ops.dequant_scale_normal(sym, hyper)
+        y_hat = grid.dequant(sym, hyper, m._synthesis.takes_s3(sym.shape[1], sym.shape[2]))
         px, sse = m._pixels(y_hat, (H, W), x)                     # the decoder's own steps from the symbols on
         return cost_z, cost_y, px, sse
 
     def _ladder(self, z, y, steps, pre=None, offsets=None):
+        dev = self.m.device
         zi, hyper = self._hyper_of(z) if pre is None else pre
-        cost_z = rans_cost(zi, channel_table_ids(z.shape, self.m.device), self.z_tables)
+        cost_z = rans_cost(zi, channel_table_ids(z.shape, dev), self.z_tables)
         if offsets is None:
-            cost_y = step_ladder_cost(y, hyper, scale_table_ids(hyper), steps, self.y_tables, self._step_tensors(steps))
+            cost_y = step_ladder_cost(y, hyper, scale_table_ids(hyper), steps, self.y_tables, step_tensors(steps, dev))
         else:
-            cost_y = step_map_ladder_cost(y, hyper, scale_table_ids(hyper), self._map_tensor(offsets), steps, self.y_tables, self._map_lut())
+            cost_y = step_map_ladder_cost(y, hyper, scale_table_ids(hyper), torch.from_numpy(offsets).to(dev), steps, self.y_tables,
+                                          cached_step_lut(dev))
         return cost_z, cost_y
 
     def ladder_cost(self, z_loc, y_loc, image_hw, steps, step_offsets=None):
@@ -1068,8 +1135,7 @@ class Codec:
         steps = check_steps(list(steps), len(steps))
         if not steps:
             raise ValueError("ladder_cost: no candidate step")
-        if self.m._precision != "fp32":
-            raise NotImplementedError(f"quantisation steps run in precision 'fp32', not {self.m._precision!r}")
+        require_fp32(self.m._precision, "a quantisation step")
         n, H, W = self._check_latents(z_loc, y_loc, image_hw)
         offsets = None if step_offsets is None else check_offsets(step_offsets, n, *y_loc.shape[1:3])
         with torch.cuda.device(self.m.device):
@@ -1088,8 +1154,7 @@ class Codec:
         steps = check_steps(list(steps), len(steps))
         if not steps:
             raise ValueError("ladder_distortion: no candidate step")
-        if m._precision != "fp32":
-            raise NotImplementedError(f"quantisation steps run in precision 'fp32', not {m._precision!r}")
+        require_fp32(m._precision, "a quantisation step")
         n, H, W = self._check_latents(z_loc, y_loc, x.shape[1:3])
         offsets = None if step_offsets is None else check_offsets(step_offsets, n, *y_loc.shape[1:3])
         with torch.cuda.device(m.device):
@@ -1097,16 +1162,17 @@ class Codec:
             _, hyper = self._hyper_of(z_loc.contiguous()) if pre is None else pre
             chunk = min(LADDER_MAX, max(1, int(chunk_bytes) // (4 * y.numel())))
             if offsets is None:
-                st, inv, _ = self._step_tensors(steps)
+                st, inv, _ = step_tensors(steps, m.device)
             else:
-                off_d, bases = self._map_tensor(offsets), torch.tensor(steps, dtype=torch.int32).to(m.device)
+                off_d, bases = torch.from_numpy(offsets).to(m.device), torch.tensor(steps, dtype=torch.int32).to(m.device)
+                lut = cached_step_lut(m.device)
             sse = torch.empty((n, len(steps)), dtype=torch.int64, device=m.device)
             for lo in range(0, len(steps), chunk):
                 k = min(chunk, len(steps) - lo)
                 if offsets is None:
                     y_hat = ops.step_ladder_dequant(y, hyper, inv[lo:lo + k], st[lo:lo + k])
                 else:
-                    y_hat = ops.step_map_ladder_dequant(y, hyper, off_d, self._map_lut(), bases[lo:lo + k])
+                    y_hat = ops.step_map_ladder_dequant(y, hyper, off_d, lut, bases[lo:lo + k])
                 _, part = m._pixels(y_hat.view((k * n,) + tuple(y.shape[1:])), (H, W), x.repeat(k, 1, 1, 1))
                 sse[:, lo:lo + k] = part.view(k, n).t()
             return sse
@@ -1164,15 +1230,14 @@ class Codec:
         n, H, W = x.shape[0], int(x.shape[1]), int(x.shape[2])
         if sum(v is not None for v in (step, target_bpp, target_psnr)) > 1:
             raise ValueError("compress: step, target_bpp and target_psnr exclude each other")
-        steps, kmap = self._quant(step, step_offsets, n, H, W)
+        grid = self._grid(step, step_offsets, n, H, W)
         budgets, offsets = None, None
         if target_bpp is not None or target_psnr is not None:
             if target_psnr is not None:
                 budgets = quality_budgets(check_quality(target_psnr, n), H, W)
             else:
                 budgets = check_budgets(target_bpp, n) * float(H * W)
-            if m._precision != "fp32":
-                raise NotImplementedError(f"quantisation steps run in precision 'fp32', not {m._precision!r}")
+            require_fp32(m._precision, "a quantisation step")
             if step_offsets is not None:
                 offsets = check_offsets(step_offsets, n, *self.latent_shapes(H, W)[4:])
                 offsets = offsets if offsets.any() else None          # all zero: today's rate control, launch for launch
@@ -1180,14 +1245,13 @@ class Codec:
             lat = m.infer_latent_rvs(x)
             z, y = lat.uq[0].loc.contiguous(), lat.uq[1].loc.contiguous()
             if budgets is None:
-                return self._finish([self._launch_latents(z, y, (H, W), steps, kmap=kmap)])[0]
+                return self._finish([self._launch_latents(z, y, (H, W), grid)])[0]
             if target_psnr is not None:
                 self.last_report, pre = self._quality_control(z, y, x, H, W, budgets, offsets)
             else:
                 self.last_report, pre = self._rate_control(z, y, H, W, budgets, offsets)
             chosen = [r["step_chosen"] for r in self.last_report]
-            steps, kmap = self._quant(chosen, offsets, n, H, W)
-            return self._finish([self._launch_latents(z, y, (H, W), steps, pre, kmap)])[0]
+            return self._finish([self._launch_latents(z, y, (H, W), self._grid(chosen, offsets, n, H, W), pre)])[0]
 
     def _rate_control(self, z, y, H, W, budget_bits, offsets=None):
         """The rate-control pass of ``compress(x, target_bpp=...)`` on given latents: the whole ladder priced in one pass, the
@@ -1221,7 +1285,7 @@ class Codec:
                     st.wait_stream(main)
                 with torch.cuda.stream(st):
                     lat = m.infer_latent_rvs(x)
-                    jobs.append(dict(self._launch_latents(lat.uq[0].loc, lat.uq[1].loc, x.shape[1:3]), st=st))
+                    jobs.append(dict(self._launch_latents(lat.uq[0].loc, lat.uq[1].loc, x.shape[1:3], StepGrid("unit", x.shape[0])), st=st))
             for j in jobs:
                 if j["st"] is not main:
                     main.wait_stream(j["st"])
@@ -1233,8 +1297,8 @@ class Codec:
         """Header and stream lengths of one blob, checked against THIS model: nothing later trusts the header."""
         mapped = len(blob) > 4 and blob[4] == VERSION_MAP          # the version byte: 3 and 5 -> parse_v3, 7 -> parse_v7
         hd = (parse_v7 if mapped else parse_v3)(blob, self.m._precision, self.latent_shapes)
-        hd.setdefault("kmap", None)
-        if (hd["steps"] is not None or mapped) and self.m._precision != "fp32":
+        hd["grid"] = StepGrid.from_header(hd)
+        if hd["grid"].kind != "unit" and self.m._precision != "fp32":
             raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream version {blob[4]} (quantisation steps) decodes in precision 'fp32' only")
         return hd
 
@@ -1271,11 +1335,11 @@ class Codec:
             host[8 * noff:].view(np.int16)[:] = np.concatenate(words)
             up = torch.from_numpy(host).to(dev)
             off_d, word_d = up[:8 * noff].view(torch.int64), up[8 * noff:].view(torch.int16)
-            # v5: every blob's step tensors go up here too, before anything is enqueued; they are read on the caller's stream only
-            stepd = [None if hd["steps"] is None else self._step_tensors(hd["steps"]) for hd in heads]
-            # v7: so do every blob's map and the step table the map kernels index
-            mapd = [None if hd["kmap"] is None else self._map_tensor(hd["kmap"]) for hd in heads]
-            lut = self._map_lut() if any(t is not None for t in mapd) else None
+            # v5 / v7: every blob's step tensors or map go up here too, before anything is enqueued; they are read on the caller's
+            # stream only
+            grids = [hd["grid"] for hd in heads]
+            for grid in grids:
+                grid.on(dev)
             pay, offd = [], []
             o = wpos = 0
             for hd in heads:
@@ -1329,11 +1393,7 @@ class Codec:
                     raise capi.SntcError(capi.ERR_BAD_SHAPE, f"hyper-synthesis output {tuple(hyper.shape)} does not match the latents "
                                          f"{(hd['n'], hd['h'], hd['w'], hd['c'])}")
                 hypers[k] = hyper
-                tidl[k] = scale_table_ids(hyper)
-                if hd["steps"] is not None:      # v5: the tables k places down the ladder, the decoder's start tables unchanged
-                    tidl[k] = step_table_ids(tidl[k], stepd[k][2])
-                if mapd[k] is not None:          # v7: the same shift per position
-                    tidl[k] = step_map_table_ids(tidl[k], mapd[k])
+                tidl[k] = grids[k].table_ids(scale_table_ids(hyper))
                 if piped:
                     launch_latents(k)
             if not piped:                    # A/B (PIPELINE_BLOBS = False), round 4's schedule: every hyper-synthesis, then every blob's
@@ -1350,12 +1410,7 @@ class Codec:
                     main.wait_stream(st)
                     syms[k].record_stream(main)
                 with ops.static_schedules(piped and i + 1 < len(order)):
-                    if mapd[k] is not None:
-                        y_hat = ops.dequant_step_map(syms[k], hypers[k], mapd[k], lut)
-                    elif hd["steps"] is not None:
-                        y_hat = ops.dequant_step(syms[k], hypers[k], stepd[k][0])
-                    else:
-                        y_hat = ops.dequant_split3(syms[k], hypers[k]) if m._synthesis.takes_s3(hd["h"], hd["w"]) else ops.dequant_scale_normal(syms[k], hypers[k])
+                    y_hat = grids[k].dequant(syms[k], hypers[k], m._synthesis.takes_s3(hd["h"], hd["w"]))
                     out[k] = m._pixels(y_hat, (hd["H"], hd["W"]))
             nbad = int(bad.sum().item())                           # synchronises the stream
             if nbad:

@@ -24,6 +24,7 @@ from ..common.latent_rvs_lib import LatentRVCollection, UQLatentRV
 from ..common.latent_rvs_utils import sga_schedule_at_step
 from ..common.train_lib import Metrics
 from ..common.transforms import class_builder as transform_builder
+from ..entropy_coding import StepGrid, require_fp32
 
 EMPTY_DICT = {}
 
@@ -608,17 +609,13 @@ class Model:
         y_hat = fma(step_size(k), symbols, mu).  ``step_offsets``: the per-position offsets they were quantised with
         (``compress(step_offsets=...)``): k = clip(step + step_offsets) per latent position."""
         self._check_step_arguments("decode", step, step_offsets=step_offsets)
-        steps, kmap = None, None
+        grid = None
         if step is not None or step_offsets is not None:
-            codec = self._get_codec()
-            steps, kmap = codec._quant(step, step_offsets, symbols.shape[0], int(image_hw[0]), int(image_hw[1]))
+            grid = self._get_codec()._grid(step, step_offsets, symbols.shape[0], int(image_hw[0]), int(image_hw[1]))
         with torch.cuda.device(self.device):
-            if kmap is not None:
-                mu = self._hyper_synthesis.leading_channels(z_hat, symbols.shape[-1])
-                y_hat = ops.dequant_step_map(symbols, mu, codec._map_tensor(kmap), codec._map_lut())
-            elif steps is not None:
-                mu = self._hyper_synthesis.leading_channels(z_hat, symbols.shape[-1])
-                y_hat = ops.dequant_step(symbols, mu, self._get_codec()._step_tensors(steps)[0])
+            if grid is not None and grid.kind != "unit":
+                grid.on(self.device)
+                y_hat = grid.dequant(symbols, self._hyper_synthesis.leading_channels(z_hat, symbols.shape[-1]))
             elif self._synthesis.takes_s3(symbols.shape[1], symbols.shape[2]):      # bf16x3: y_hat leaves the dequantisation pre-split
                 y_hat = ops.dequant_split3(symbols, self._hyper_synthesis(z_hat))
             else:     # mu only: the last hyper-synthesis layer skips its raw-sigma columns where its plan can (same bits)
@@ -805,9 +802,7 @@ class Model:
         if itinf is not None:
             raise ValueError(f"{where}: step / target_bpp / step_offsets and itinf exclude each other at the top level (they travel "
                              "inside the itinf dict)")
-        if self._precision != "fp32":
-            raise NotImplementedError(f"{where}(step / target_bpp / step_offsets) runs in precision 'fp32', not {self._precision!r}: "
-                                      "the pre-split dequantisation is not extended")
+        require_fp32(self._precision, f"{where}(step / target_bpp / step_offsets)")
 
     def step_offsets_shape(self, H, W):
         """(h, w) of ``step_offsets`` for H x W images: the resolution of the latents y (``Codec.latent_shapes``)."""
@@ -848,17 +843,13 @@ class Model:
         if ssim:
             ops.msssim_scale_sizes(h, w)                              # ValueError before any launch
         codec = self._get_codec()
-        kw = {} if step is None else dict(step=codec._steps(step, n))
-        if step_offsets is not None:
-            from ..entropy_coding import check_offsets
-            kw["step_offsets"] = check_offsets(step_offsets, n, *codec.latent_shapes(h, w)[4:])       # ValueError before any launch
+        kw = {}
+        if step is not None or step_offsets is not None:
+            kw = dict(step=step, step_offsets=step_offsets)
+            grid = codec._grid(step, step_offsets, n, h, w)           # ValueError before any launch
         if weighted:
-            from ..entropy_coding import check_steps, index_map, position_weights
-            lh, lw = codec.latent_shapes(h, w)[4:]
             block = self._position_block(h, w)
-            offs = kw.get("step_offsets")
-            omega = position_weights(index_map(check_steps(0 if step is None else step, n),
-                                               np.zeros((n, lh, lw), np.int8) if offs is None else offs))
+            omega = grid.position_weights(*codec.latent_shapes(h, w)[4:])
         with torch.cuda.device(self.device):
             if latent_rvs is None:
                 latent_rvs = self.infer_latent_rvs(x)
@@ -901,32 +892,24 @@ class Model:
     def _compress_itinf(self, x, steps, seed=0, check_every=None, step=None, rd_lambda=None, target_bpp=None, step_offsets=None):
         if self._latent_config["uq"].get("method", "unoise") != "sga":       # every refusal before any launch
             raise NotImplementedError("itinf_train_step implements latent_config uq.method == 'sga'")
-        if self._precision != "fp32":
-            raise NotImplementedError(f"compress(itinf=...) runs in precision 'fp32', not {self._precision!r}")
+        require_fp32(self._precision, "compress(itinf=...)")
         steps = int(steps)
         if steps < 0 or (check_every is not None and int(check_every) < 1):
             raise ValueError("compress(itinf=...): steps >= 0, check_every None or >= 1")
-        mapped = step_offsets is not None
-        stepped = mapped or step is not None or target_bpp is not None or rd_lambda is not None
-        n = 1 if len(tuple(x.shape)) == 3 else int(x.shape[0])
-        budgets = info = None
-        if mapped:
+        stepped = step_offsets is not None or step is not None or target_bpp is not None or rd_lambda is not None
+        shape = tuple(x.shape)
+        n = 1 if len(shape) == 3 else int(shape[0])
+        budgets = q = None
+        if stepped:
             from ..entropy_coding import check_budgets
-            info = self._itinf_map_of(tuple(x.shape), step, rd_lambda, step_offsets, target_bpp)
-            if target_bpp is not None:
-                budgets = check_budgets(target_bpp, n)
-        elif stepped:
-            from ..entropy_coding import check_budgets
-            if step is not None and target_bpp is not None:
-                raise ValueError("compress(itinf=...): step and target_bpp exclude each other")
-            quant = self._itinf_quant_of(n, 0 if step is None else step, rd_lambda)
+            q = self._itinf_grid_of(shape, step, rd_lambda, step_offsets, target_bpp)
             if target_bpp is not None:
                 budgets = check_budgets(target_bpp, n)
         x = self._as_device_images(x)
         if self._distortion == "ms_ssim":
             ops.msssim_scale_sizes(x.shape[1], x.shape[2])
         codec = self._get_codec()
-        kmap = None
+        mapped = False
         if not stepped:
             self.initialize_itinf(x)
             cost_kw = lat_kw = {}
@@ -936,30 +919,24 @@ class Model:
             flushed = float(codec.flushed_bits(H, W))
             self.initialize_itinf(x)
             control = None
-            base = info["steps"] if mapped else None
             if budgets is not None:             # the steps of compress(x, target_bpp=b): chosen from the encoder's latents, once
                 budgets = budgets * float(H * W)
-                offs = info["offsets"] if mapped and info["offsets"].any() else None      # all zero: today's rate control
+                offs = None if q is None else q["offsets"]
+                offs = offs if offs is not None and offs.any() else None      # all zero: today's rate control
                 with torch.cuda.device(self.device):
                     control = codec._rate_control(*[rv.loc.contiguous() for rv in self.latent_rvs.uq], H, W, budgets, offs)[0]
-                base = [r["step_chosen"] for r in control]
-                if not mapped:
-                    quant = self._itinf_quant_of(n, base, rd_lambda)
-            if mapped:                          # Codec._quant's routing: only a map that varies inside an image is a map
-                uniform, kmap = codec._quant(base, info["offsets"], n, H, W)
-                if kmap is None:
-                    quant = self._itinf_quant_of(n, 0 if uniform is None else uniform, None)
-            if kmap is None:
-                self._set_itinf_quant(quant)
-                ks = [0] * n if quant is None else quant["steps"]
+                q = self._itinf_grid_of(shape, [r["step_chosen"] for r in control], rd_lambda, step_offsets)
+            self._set_itinf_grid(q)
+            mapped = q is not None and q["grid"].kind == "map"      # only a map that varies inside an image is a map
+            if mapped:
+                ks = q["steps"]
+                lat_kw = dict(step=ks, step_offsets=q["offsets"])
+                cost_kw = dict(lat_kw, weighted=True)                         # J with the weight on every position's pixels
+            else:
+                ks = [0] * n if q is None else q["grid"].steps
                 lams = step_lambdas(self._rd_lambda, ks, rd_lambda)
                 lat_kw = dict(step=ks) if any(ks) else {}
                 cost_kw = dict(lat_kw, lam=lams)                              # J at each image's own step and weight
-            else:
-                self._set_itinf_map(dict(kmap=kmap, block=info["block"]))
-                ks = base
-                lat_kw = dict(step=ks, step_offsets=info["offsets"])
-                cost_kw = dict(lat_kw, weighted=True)                         # J with the weight on every position's pixels
 
         def cost_of(latents):
             return self.coded_cost(x, latents, **cost_kw)
@@ -968,7 +945,7 @@ class Model:
             start = cost_of(self.latent_rvs)
             best = [rv.loc.clone() for rv in self.latent_rvs.uq]
             j_best, bits_best, step_best = start["J"].copy(), start["bits"].copy(), np.zeros(n, np.int64)
-            blocks_best = start["sse_blocks"].copy() if kmap is not None else None
+            blocks_best = start["sse_blocks"].copy() if mapped else None
             met = None if budgets is None else np.array([r["met"] for r in control], bool)
             room = budgets                      # what a candidate's bits + flushed states may reach: the budget less the map's records
             if budgets is not None and "map_bits" in control[0]:
@@ -991,10 +968,10 @@ class Model:
                                           bits_start=float(start["bits"][i]), bits_chosen=float(bits_best[i])) for i in range(n)]
         if stepped:
             for i, r in enumerate(self.last_compress_report):
-                if kmap is None:
-                    r.update(quant_step=int(ks[i]), lam=float(lams[i]))
-                else:
+                if mapped:
                     r.update(quant_step=int(ks[i]), weighted=True, sse_blocks=blocks_best[i].copy())
+                else:
+                    r.update(quant_step=int(ks[i]), lam=float(lams[i]))
                 if budgets is not None:
                     r.update(budget_bits=float(budgets[i]), met=bool(met[i]))
                     if "map_bits" in control[i]:
@@ -1036,26 +1013,17 @@ class Model:
         """latent_rvs = trainable copy of the encoder's latents; fresh Adam state (:389-395).
         ``step`` (a ladder index, or one per image) / ``rd_lambda`` (a number, or one per image; default
         lambda / step_size(k_i)^2): the steps that follow descend the loss at those quantisation steps,
-        mean_B(bits_i) / (H W) + (1 / n) sum_i lambda_i D_i (sga.SGAEngine.loss_and_grads(quant=...)).  Every index 0
+        mean_B(bits_i) / (H W) + (1 / n) sum_i lambda_i D_i (sga.SGAEngine.loss_and_grads(grid=...)).  Every index 0
         and no ``rd_lambda``: the steps of before, launch for launch.
         ``step_offsets`` (integers [n, h, w] as in ``compress``): the steps that follow descend the loss on the map
         K_i[p] = clip(step_i + step_offsets[i, p]), mean_B(bits_i) / (H W) + (lambda / n) sum_i Dw_i with the weight
-        1 / step_size(K_i[p])^2 on the pixels of position p (sga.SGAEngine.loss_and_grads(quant_map=...)); MSE only,
+        1 / step_size(K_i[p])^2 on the pixels of position p (sga.SGAEngine.loss_and_grads(grid=...)); MSE only,
         and ``rd_lambda`` is refused with it.  All-zero offsets are the steps of before and a map constant per image those of
         ``step`` = its indexes, launch for launch; only a map that varies inside an image takes the map kernels."""
         from ..sga import SGAEngine
         if self._optimizer_config.get("global_clipnorm") is not None:
             raise NotImplementedError("gradient clipping is not used by the reference's itinf config")
-        shape = tuple(image_batch.shape)
-        n = 1 if len(shape) == 3 else shape[0]
-        mapq = None
-        if step_offsets is None:
-            quant = self._itinf_quant_of(n, step, rd_lambda)            # every refusal before any launch
-        else:
-            info = self._itinf_map_of(shape, step, rd_lambda, step_offsets)
-            uniform, kmap = self._get_codec()._quant(info["steps"], info["offsets"], n, int(shape[-3]), int(shape[-2]))
-            quant = None if kmap is not None else self._itinf_quant_of(n, 0 if uniform is None else uniform, None)
-            mapq = None if kmap is None else dict(kmap=kmap, block=info["block"])
+        q = self._itinf_grid_of(tuple(image_batch.shape), step, rd_lambda, step_offsets)     # every refusal before any launch
         if self._distortion == "ms_ssim":                               # ValueError where the loss is not computable
             ops.msssim_scale_sizes(*tuple(image_batch.shape)[1:3])
         self.latent_rvs = self.infer_latent_rvs(image_batch).get_trainable_copy()
@@ -1064,62 +1032,52 @@ class Model:
         self.itinf = True
         self._itinf_step = 0
         self._itinf_pending = None
-        self._set_itinf_quant(quant)
-        self._set_itinf_map(mapq)
+        self._set_itinf_grid(q)
 
-    def _itinf_map_of(self, shape, step, rd_lambda, step_offsets, target_bpp=None):
-        """The host half of SGA on a step map (``initialize_itinf(step_offsets=)``, ``compress(itinf=dict(step_offsets=))``): every
-        refusal, before any launch.  -> dict(steps = the n base indexes, offsets int8 [n, h, w], block = pixels per position)."""
+    def _itinf_grid_of(self, shape, step, rd_lambda, step_offsets, target_bpp=None):
+        """The host half of SGA on a quantisation grid (``initialize_itinf(step=, rd_lambda=, step_offsets=)``, ``compress(itinf=
+        dict(...))``): every refusal, before any launch, then ``StepGrid.resolve``'s routing.  -> None (step 1 and the model's lambda
+        for every image: the kernels of before) or dict(grid, steps = the n base indexes, offsets = int8 [n, h, w] or None,
+        lam = each image's lambda (None on a map), block = pixels per position (with offsets))."""
+        if step is None and rd_lambda is None and step_offsets is None and target_bpp is None:
+            return None
         from ..entropy_coding import check_offsets, check_steps
         if self.factorized:
-            raise NotImplementedError("SGA on a step map (step_offsets): mean-scale hyperprior models only")
-        if self._precision != "fp32":
-            raise NotImplementedError(f"SGA on a step map runs in precision 'fp32', not {self._precision!r}")
-        if self._distortion == "ms_ssim":
+            raise NotImplementedError("SGA at a quantisation step (step / rd_lambda / step_offsets): mean-scale hyperprior models only")
+        require_fp32(self._precision, "SGA at a quantisation step")
+        if step_offsets is not None and self._distortion == "ms_ssim":
             raise NotImplementedError("SGA on a step map descends the weighted MSE: distortion='ms_ssim' with step_offsets is not implemented")
-        if rd_lambda is not None:
+        if step_offsets is not None and rd_lambda is not None:
             raise ValueError("rd_lambda and step_offsets exclude each other: a weight per image and a weight per position are not both defined")
         if step is not None and target_bpp is not None:
             raise ValueError("compress(itinf=...): step and target_bpp exclude each other")
         n = 1 if len(shape) == 3 else int(shape[0])
+        ks = check_steps(0 if step is None else step, n)
+        if step_offsets is None:                                        # a per-image lambda keeps the per-image kernels at step 0
+            lams = step_lambdas(self._rd_lambda, ks, rd_lambda)         # iterative inference runs at the model's own lambda
+            return dict(grid=StepGrid.image(ks), steps=ks, offsets=None, lam=lams, block=None) if any(ks) or rd_lambda is not None else None
         H, W = int(shape[-3]), int(shape[-2])
-        ks = check_steps(0 if step is None else step, n)
-        offs = check_offsets(step_offsets, n, *self._get_codec().latent_shapes(H, W)[4:])
-        return dict(steps=ks, offsets=offs, block=self._position_block(H, W))
-
-    def _set_itinf_map(self, mapq):
-        """``mapq`` = dict(kmap = absolute indexes int8 [n, h, w] on the host, block) or None: the device tensors of the map
-        kernels (the map, the coder's step table, the float32 position weights), one small upload each."""
-        if mapq is not None:
-            from ..entropy_coding import position_weights
-            codec = self._get_codec()
-            with torch.cuda.device(self.device):
-                mapq["tensors"] = (codec._map_tensor(mapq["kmap"]), codec._map_lut(),
-                                   ops.to_device(position_weights(mapq["kmap"]), self.device), int(mapq["block"]))
-            self._itinf_quant = None
-        self._itinf_map = mapq
-
-    def _itinf_quant_of(self, n, step, rd_lambda):
-        """The host half of ``initialize_itinf(step=, rd_lambda=)``: the refusals, the ladder indexes and each image's lambda.
-        -> None (step 1 and the model's lambda for every image: the kernels of before) or dict(steps, lam)."""
-        if step is None and rd_lambda is None:
+        h, w = self._get_codec().latent_shapes(H, W)[4:]
+        offs = check_offsets(step_offsets, n, h, w)
+        block = self._position_block(H, W)
+        grid = StepGrid.resolve(ks, offs, n, h, w)
+        if grid.kind == "unit":
             return None
-        from ..entropy_coding import check_steps
-        if self.factorized:
-            raise NotImplementedError("SGA at a quantisation step (step / rd_lambda): mean-scale hyperprior models only")
-        if self._precision != "fp32":
-            raise NotImplementedError(f"SGA at a quantisation step runs in precision 'fp32', not {self._precision!r}")
-        ks = check_steps(0 if step is None else step, n)
-        lams = step_lambdas(self._rd_lambda, ks, rd_lambda)             # iterative inference runs at the model's own lambda
-        return dict(steps=ks, lam=lams) if any(ks) or rd_lambda is not None else None
+        lams = None if grid.kind == "map" else step_lambdas(self._rd_lambda, grid.steps)
+        return dict(grid=grid, steps=ks, offsets=offs, lam=lams, block=block)
 
-    def _set_itinf_quant(self, quant):
-        if quant is not None:
-            from ..entropy_coding import step_tensors
+    def _set_itinf_grid(self, q):
+        """``q`` of ``_itinf_grid_of``: what the SGA kernels read goes up (one small upload each), with the distortion weight
+        that goes with the grid -- a map: (the float32 position weights, block); else dweight = lambda_i / lambda, the distortion
+        gradient being launched with the scalar lambda."""
+        if q is not None:
             with torch.cuda.device(self.device):
-                dweight = ops.to_device(quant["lam"] / float(self._rd_lambda), self.device)   # the distortion gradient is launched
-                quant["tensors"] = tuple(step_tensors(quant["steps"], self.device)) + (dweight,)    # with the scalar lambda
-        self._itinf_quant = quant
+                q["grid"].on(self.device)
+                if q["grid"].kind == "map":
+                    q["weight"] = (ops.to_device(q["grid"].position_weights(), self.device), int(q["block"]))
+                else:
+                    q["weight"] = ops.to_device(q["lam"] / float(self._rd_lambda), self.device)
+        self._itinf_grid = q
 
     @property
     def itinf_trainable_variables(self):
@@ -1141,12 +1099,9 @@ class Model:
         tau = cfg["tau"]
         lr = self._scheduled_lr
         locs = [rv.loc for rv in self.latent_rvs.uq]                     # (z_loc, y_loc); the factorized model: (y_loc,)
-        q = getattr(self, "_itinf_quant", None)
-        qm = getattr(self, "_itinf_map", None)
+        q = getattr(self, "_itinf_grid", None)
         with torch.cuda.device(self.device):
-            quant = {} if q is None else dict(quant=q["tensors"])
-            if qm is not None:
-                quant = dict(quant_map=qm["tensors"])
+            quant = {} if q is None else dict(grid=q["grid"], weight=q["weight"])
             r = self._sga.loss_and_grads(x, locs[0] if len(locs) == 2 else None, locs[-1], tau, self._scheduled_rd_lambda,
                                          step=self._itinf_step, seed=seed,
                                          noise_z=None if noise is None else noise[0],
@@ -1160,7 +1115,7 @@ class Model:
             rows = [r["bits_z"], r["bits_y"], r["sse"]] + ([r["msssim"]] if "msssim" in r else []) + ([r["wsse"]] if "wsse" in r else [])
             self._itinf_pending = dict(dev=torch.stack(rows), shape=tuple(x.shape), two=len(locs) == 2,
                                        scalars=(self._scheduled_lr, self._scheduled_rd_lambda, tau),
-                                       lams=None if q is None or qm is not None else q["lam"], weighted="wsse" in r)
+                                       lams=None if q is None else q["lam"], weighted="wsse" in r)
         self._itinf_step += 1
         self.last_grads = tuple(grads)
         return self.itinf_last_metrics() if fetch else None

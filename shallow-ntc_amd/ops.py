@@ -1444,19 +1444,35 @@ def _check_quant(quant, count, n, device):
     return quant
 
 
-def sga_normal_step_fwd(y_loc, hyper, tau, quant, noise=None, seed=0, step=0):
-    """``sga_normal_fwd`` at one quantisation step per image: ``quant`` = (step_size, inv_step, shift[, dweight]) as
-    entropy_coding.step_tensors makes them; ``step`` stays the SGA step number of the generator.
-    -> (y_tilde = fma(step_size, v, mu), sprime = d v / d u, dbits_dv, dbits_draw, bits[n]), v the sample on the step's grid."""
+def _check_sga_step_fwd(y_loc, hyper, noise):
+    """What the step and map forward kernels share: NHWC latents, hyper = [mu | raw sigma] of the same positions, Gumbel pairs.
+    -> (n, hw, c)."""
     _check_nhwc(y_loc)
     c = y_loc.shape[-1]
     _check_nhwc(hyper, 2 * c)
-    n, hw = y_loc.shape[0], y_loc.shape[1] * y_loc.shape[2]
     if tuple(hyper.shape[:3]) != tuple(y_loc.shape[:3]):
         raise ValueError(f"hyper-synthesis output {tuple(hyper.shape)} does not match latents {tuple(y_loc.shape)}")
     if noise is not None and not (isinstance(noise, torch.Tensor) and noise.is_cuda and noise.dtype == torch.float32
                                   and noise.is_contiguous() and tuple(noise.shape) == tuple(y_loc.shape) + (2,)):
         raise ValueError("noise: contiguous float32 Gumbel pairs shaped like y_loc + (2,)")
+    return y_loc.shape[0], y_loc.shape[1] * y_loc.shape[2], c
+
+
+def _check_sga_step_bwd(g_ytilde, cached, where):
+    """What the step and map backward kernels share: the forward's ``cached`` tensors shaped like the gradient."""
+    _check_nhwc(g_ytilde)
+    for t in cached:
+        _check_nhwc(t, g_ytilde.shape[-1])
+        if tuple(t.shape) != tuple(g_ytilde.shape):
+            raise ValueError(f"{where}: {tuple(t.shape)} does not match the gradient {tuple(g_ytilde.shape)}")
+    return g_ytilde.shape
+
+
+def sga_normal_step_fwd(y_loc, hyper, tau, quant, noise=None, seed=0, step=0):
+    """``sga_normal_fwd`` at one quantisation step per image: ``quant`` = (step_size, inv_step, shift[, dweight]) as
+    entropy_coding.step_tensors makes them; ``step`` stays the SGA step number of the generator.
+    -> (y_tilde = fma(step_size, v, mu), sprime = d v / d u, dbits_dv, dbits_draw, bits[n]), v the sample on the step's grid."""
+    n, hw, c = _check_sga_step_fwd(y_loc, hyper, noise)
     st, inv, sh = _check_quant(quant, 3, n, y_loc.device)
     yt, sp, dv, dr = (torch.empty_like(y_loc) for _ in range(4))
     bits = torch.empty((n,), dtype=torch.float64, device=y_loc.device)
@@ -1468,12 +1484,7 @@ def sga_normal_step_fwd(y_loc, hyper, tau, quant, noise=None, seed=0, step=0):
 def sga_normal_step_bwd(g_ytilde, sprime, dbits_dv, dbits_draw, weight, quant):
     """``sga_normal_bwd`` at one quantisation step per image, ``quant`` = (step_size, inv_step, shift, dweight): dweight[i]
     multiplies image i's distortion gradient.  -> (g_yloc, g_hyper[.., 2C])."""
-    _check_nhwc(g_ytilde)
-    n, h, w, c = g_ytilde.shape
-    for t in (sprime, dbits_dv, dbits_draw):
-        _check_nhwc(t, c)
-        if tuple(t.shape) != tuple(g_ytilde.shape):
-            raise ValueError(f"sga_normal_step_bwd: {tuple(t.shape)} does not match the gradient {tuple(g_ytilde.shape)}")
+    n, h, w, c = _check_sga_step_bwd(g_ytilde, (sprime, dbits_dv, dbits_draw), "sga_normal_step_bwd")
     st, inv, _, dw = _check_quant(quant, 4, n, g_ytilde.device)
     g_y = torch.empty_like(g_ytilde)
     g_h = torch.empty((n, h, w, 2 * c), dtype=torch.float32, device=g_ytilde.device)
@@ -1488,15 +1499,7 @@ def sga_normal_step_map_fwd(y_loc, hyper, tau, kmap, lut, noise=None, seed=0, st
     of step_size(k) and the rate is that of the table k places down the ladder; a map constant per image gives
     ``sga_normal_step_fwd``'s outputs at those indexes, bit for bit.
     -> (y_tilde = fma(step_size(k), v, mu), sprime = d v / d u, dbits_dv, dbits_draw, bits[n])."""
-    _check_nhwc(y_loc)
-    c = y_loc.shape[-1]
-    _check_nhwc(hyper, 2 * c)
-    n, hw = y_loc.shape[0], y_loc.shape[1] * y_loc.shape[2]
-    if tuple(hyper.shape[:3]) != tuple(y_loc.shape[:3]):
-        raise ValueError(f"hyper-synthesis output {tuple(hyper.shape)} does not match latents {tuple(y_loc.shape)}")
-    if noise is not None and not (isinstance(noise, torch.Tensor) and noise.is_cuda and noise.dtype == torch.float32
-                                  and noise.is_contiguous() and tuple(noise.shape) == tuple(y_loc.shape) + (2,)):
-        raise ValueError("noise: contiguous float32 Gumbel pairs shaped like y_loc + (2,)")
+    n, hw, c = _check_sga_step_fwd(y_loc, hyper, noise)
     _check_step_map(y_loc, kmap, lut, "sga_normal_step_map_fwd")
     yt, sp, dv, dr = (torch.empty_like(y_loc) for _ in range(4))
     bits = torch.empty((n,), dtype=torch.float64, device=y_loc.device)
@@ -1508,12 +1511,7 @@ def sga_normal_step_map_fwd(y_loc, hyper, tau, kmap, lut, noise=None, seed=0, st
 def sga_normal_step_map_bwd(g_ytilde, sprime, dbits_dv, dbits_draw, weight, kmap, lut):
     """``sga_normal_step_bwd`` with one ladder index per latent position and no per-image weight on the distortion gradient
     (on a map the weight sits on the pixels: ``distortion_grad_weighted``).  -> (g_yloc, g_hyper[.., 2C])."""
-    _check_nhwc(g_ytilde)
-    n, h, w, c = g_ytilde.shape
-    for t in (sprime, dbits_dv, dbits_draw):
-        _check_nhwc(t, c)
-        if tuple(t.shape) != tuple(g_ytilde.shape):
-            raise ValueError(f"sga_normal_step_map_bwd: {tuple(t.shape)} does not match the gradient {tuple(g_ytilde.shape)}")
+    n, h, w, c = _check_sga_step_bwd(g_ytilde, (sprime, dbits_dv, dbits_draw), "sga_normal_step_map_bwd")
     _check_step_map(g_ytilde, kmap, lut, "sga_normal_step_map_bwd")
     g_y = torch.empty_like(g_ytilde)
     g_h = torch.empty((n, h, w, 2 * c), dtype=torch.float32, device=g_ytilde.device)

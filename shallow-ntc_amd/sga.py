@@ -14,6 +14,7 @@ from . import _capi as capi
 from . import ops
 from .common._graph import GDN, Conv, Seq
 from .common.transforms import _TwoLayerBase
+from .entropy_coding import StepGrid
 
 _MASKS = {None: None, "relu": capi.EPI_MASK_RELU, "leaky_relu": capi.EPI_MASK_LEAKY}
 
@@ -138,39 +139,34 @@ class SGAEngine:
             self.hyper = None if model.factorized else GradChain(model._hyper_synthesis)
             self.syn = make_backward(model._synthesis)
 
-    def loss_and_grads(self, x, z_loc, y_loc, tau, rd_lambda, step=0, seed=0, noise_z=None, noise_y=None, quant=None,
-                       quant_map=None):
-        """``quant`` = (step_size, inv_step, shift, dweight), one entry per image on the device (entropy_coding.step_tensors and
-        lambda_i / rd_lambda): the loss at a quantisation step, mean_B(bits_i) / (H W) + (1 / n) sum_i lambda_i D_i with y - mu on
-        the step's grid and the rate under the table shift places down the ladder.  The distortion gradient is
-        launched with the scalar ``rd_lambda``; the backward pass is linear in it, so lambda_i enters as dweight in the one
-        step-aware backward kernel.  None: step 1, the launches of before.
-        ``quant_map`` = (kmap int8 [n, h, w], lut = entropy_coding.step_lut, weights float32 [n, h, w] = position_weights(kmap),
-        block), all on the device: the loss on a step map, mean_B(bits_i) / (H W) + (lambda / n) sum_i Dw_i with
-        y - mu on each position's own grid, the rate under the table K_p places down the ladder, and
-        Dw_i = sum_pixels omega_i(pixel) (255 (x - x_hat))^2 / (H W C), a pixel taking the weight of the position whose block x block
-        square it lies in.  The weight varies inside an image, so it cannot be applied after the synthesis adjoint: it sits in
-        the distortion kernel (``ops.distortion_grad_weighted``, launched with the scalar ``rd_lambda``), and the map backward
-        kernel has no dweight.  The result gains ``wsse``[n] = Dw_i H W C; ``sse`` stays unweighted.  MSE only; ``quant`` and
-        ``quant_map`` exclude each other."""
+    def loss_and_grads(self, x, z_loc, y_loc, tau, rd_lambda, step=0, seed=0, noise_z=None, noise_y=None, grid=None, weight=None):
+        """``grid`` (entropy_coding.StepGrid; None: the unit grid, the launches of before) says how y - mu is quantised, ``weight``
+        is the distortion weight that goes with it.
+        An image grid: ``weight`` = dweight float32 [n] on the device, lambda_i / rd_lambda.  The loss at a quantisation step,
+        mean_B(bits_i) / (H W) + (1 / n) sum_i lambda_i D_i with y - mu on the step's grid and the rate under the table shift places
+        down the ladder.  The distortion gradient is launched with the scalar ``rd_lambda``; the backward pass is linear in it, so
+        lambda_i enters as dweight in the one step-aware backward kernel.
+        A map grid: ``weight`` = (weights float32 [n, h, w] = position_weights(kmap) on the device, block).  The loss on a step map,
+        mean_B(bits_i) / (H W) + (lambda / n) sum_i Dw_i with y - mu on each position's own grid, the rate under the table K_p places
+        down the ladder, and Dw_i = sum_pixels omega_i(pixel) (255 (x - x_hat))^2 / (H W C), a pixel taking the weight of the position
+        whose block x block square it lies in.  The weight varies inside an image, so it cannot be applied after the synthesis
+        adjoint: it sits in the distortion kernel (``ops.distortion_grad_weighted``, launched with the scalar ``rd_lambda``), and the
+        map backward kernel has no dweight.  The result gains ``wsse``[n] = Dw_i H W C; ``sse`` stays unweighted.  MSE only."""
         m = self.m
-        if quant is not None and quant_map is not None:
-            raise ValueError("loss_and_grads: quant (one step per image) and quant_map (one per position) exclude each other")
-        if (quant is not None or quant_map is not None) and m.factorized:
+        mapped = grid is not None and grid.kind == "map"
+        if grid is not None and grid.kind != "unit" and m.factorized:
             raise NotImplementedError("SGA at a quantisation step: mean-scale hyperprior models only")
-        if quant_map is not None:
+        if mapped:
             if self.distortion != "mse":
                 raise NotImplementedError("SGA on a step map descends the weighted MSE only, not distortion='ms_ssim'")
-            if not isinstance(quant_map, (tuple, list)) or len(quant_map) != 4:
-                raise ValueError("quant_map: (kmap, lut, weights, block)")
-            kmap, lut, weights, block = quant_map
+            weights, block = weight
         n, h, w, c = x.shape
         w_bpp = 1.0 / (n * h * w)                                      # bpp = mean_B(bits) / (H W)   (:302-307)
         scale = rd_lambda * 2.0 * 255.0 * 255.0 / (n * h * w * c)     # d(lambda * mean_B mean_HWC (255 d)^2)/d x_hat
         extra = {}
 
         def distortion_grad(recon):
-            if quant_map is not None:
+            if mapped:
                 g_x, sse, extra["wsse"] = ops.distortion_grad_weighted(x, recon, scale, weights, block)
                 return g_x, sse
             if self.distortion == "mse":
@@ -185,23 +181,14 @@ class SGAEngine:
             g_y = ops.sga_chain(self.syn.backward(g_x, cache), dby, sp_y, w_bpp)
             return dict(bits_z=torch.zeros_like(bits_y), bits_y=bits_y, sse=sse, g_z=None, g_y=g_y, recon=recon, z_tilde=None,
                         y_tilde=y_t, **extra)
+        grid = StepGrid("unit", n) if grid is None else grid
         z_t, sp_z, dbz, bits_z = ops.sga_factorized_fwd(m._get_prior(), z_loc, tau, noise_z, seed, step)     # :262-268
         hyper, acts = self.hyper.forward(z_t)                                                              # :273
-        if quant_map is not None:
-            y_t, sp_y, dv, dr, bits_y = ops.sga_normal_step_map_fwd(y_loc, hyper, tau, kmap, lut, noise_y, seed, step)
-        elif quant is None:
-            y_t, sp_y, dv, dr, bits_y = ops.sga_normal_fwd(y_loc, hyper, tau, noise_y, seed, step)         # :285-291
-        else:
-            y_t, sp_y, dv, dr, bits_y = ops.sga_normal_step_fwd(y_loc, hyper, tau, quant, noise_y, seed, step)
+        y_t, sp_y, dv, dr, bits_y = grid.sga_fwd(y_loc, hyper, tau, noise_y, seed, step)                   # :285-291
         recon, cache = self.syn.forward(y_t)
         g_x, sse = distortion_grad(recon)                                                                  # :313-317,343
         g_yt = self.syn.backward(g_x, cache)
-        if quant_map is not None:
-            g_y, g_hyper = ops.sga_normal_step_map_bwd(g_yt, sp_y, dv, dr, w_bpp, kmap, lut)
-        elif quant is None:
-            g_y, g_hyper = ops.sga_normal_bwd(g_yt, sp_y, dv, dr, w_bpp)
-        else:
-            g_y, g_hyper = ops.sga_normal_step_bwd(g_yt, sp_y, dv, dr, w_bpp, quant)
+        g_y, g_hyper = grid.sga_bwd(g_yt, sp_y, dv, dr, w_bpp, None if mapped else weight)
         g_zt = self.hyper.backward(g_hyper, acts)
         g_z = ops.sga_chain(g_zt, dbz, sp_z, w_bpp)
         return dict(bits_z=bits_z, bits_y=bits_y, sse=sse, g_z=g_z, g_y=g_y, recon=recon, z_tilde=z_t, y_tilde=y_t, **extra)

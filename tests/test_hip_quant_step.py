@@ -378,10 +378,11 @@ def test_stepped_file(n, h, w, steps, dev, hyper_model):
     x = images(n, h, w, dev)
     blob = model.compress(x, step=steps)
     assert blob[:4] == b"SNTC" and blob[4] == 5
-    assert codec._parse(blob)["steps"] == steps
+    hd = codec._parse(blob)
+    assert hd["steps"] == steps and hd["grid"].kind == "image" and hd["grid"].steps == steps
     # decompress = decode of the step symbols at that step; the symbols are the float32 rule on the encoder's y and mu
     z, y = latents(model, x)
-    zi, _, sym, ytid, hyper = codec._symbols(z, y, steps)
+    zi, _, sym, ytid, hyper = codec._symbols(z, y, ec.StepGrid.image(steps))
     c = y.shape[-1]
     want_sym, want_tid, _ = np_step_symbols(y.cpu().numpy(), hyper[..., :c].cpu().numpy(), ec.scale_table_ids(hyper).cpu().numpy(), steps)
     np.testing.assert_array_equal(sym.cpu().numpy(), want_sym)

@@ -243,7 +243,8 @@ def test_sga_loss_and_gradients_at_a_step(dev):
     n, H, W, _ = x.shape
     model.initialize_itinf(x, step=ks)
     lams = step_lambdas(lam, ks)
-    assert model._itinf_quant["lam"].tolist() == lams.tolist() == [lam / ec.step_size(k) ** 2 for k in ks]
+    assert model._itinf_grid["grid"].kind == "image" and model._itinf_grid["grid"].steps == ks
+    assert model._itinf_grid["lam"].tolist() == lams.tolist() == [lam / ec.step_size(k) ** 2 for k in ks]
     z0 = model.latent_rvs.uq[0].loc.cpu().numpy().astype(np.float64)
     y0 = model.latent_rvs.uq[1].loc.cpu().numpy().astype(np.float64)
     rng = np.random.default_rng(3)
@@ -268,7 +269,7 @@ def test_sga_loss_and_gradients_at_a_step(dev):
         return ((bz + by) / (H * W) + lams[i] * mse) / n
 
     r = model._sga.loss_and_grads(t(x, dev), t(z0, dev), t(y0, dev), tau, lam, noise_z=t(gz, dev), noise_y=t(gy, dev),
-                                  quant=model._itinf_quant["tensors"])
+                                  grid=model._itinf_grid["grid"], weight=model._itinf_grid["weight"])
     bits_z, bits_y, sse = (r[k].cpu().numpy() for k in ("bits_z", "bits_y", "sse"))
     g_z, g_y = r["g_z"].cpu().numpy(), r["g_y"].cpu().numpy()
     hstep = 1e-4

@@ -364,7 +364,8 @@ def test_sga_loss_and_gradients_on_a_map(dev):
     off[1] = off[1].T
     model.initialize_itinf(x, step=ks, step_offsets=off)
     K = ec.index_map(ks, off)
-    assert model._itinf_quant is None and (model._itinf_map["kmap"] == K).all() and model._itinf_map["block"] == 16
+    q = model._itinf_grid
+    assert q["grid"].kind == "map" and q["lam"] is None and (q["grid"].kmap == K).all() and q["block"] == 16 and q["weight"][1] == 16
     assert all(len(np.unique(K[i])) == 3 for i in range(n))
     step, inv = position_steps(K)
     omega = ec.position_weights(K)
@@ -393,7 +394,7 @@ def test_sga_loss_and_gradients_on_a_map(dev):
         return ((bz + by) / (H * W) + lam * wsse / (H * W * 3)) / n
 
     r = model._sga.loss_and_grads(t(x, dev), t(z0, dev), t(y0, dev), tau, lam, noise_z=t(gz, dev), noise_y=t(gy, dev),
-                                  quant_map=model._itinf_map["tensors"])
+                                  grid=q["grid"], weight=q["weight"])
     bits_z, bits_y, sse, wsse = (r[k].cpu().numpy() for k in ("bits_z", "bits_y", "sse", "wsse"))
     g_z, g_y = r["g_z"].cpu().numpy(), r["g_y"].cpu().numpy()
     hstep = 1e-4
@@ -430,9 +431,9 @@ def test_sga_loss_and_gradients_on_a_map(dev):
     assert abs(m["bpp"] - bpp) < 1e-6 * bpp and abs(m["mse"] - mses.mean()) < 1e-6 * mses.mean() and m["sched_rd_lambda"] == lam
     # a constant map and all zeros take the per-image route and the route of before
     model.initialize_itinf(x, step=[-9, 4], step_offsets=np.full((2, 4, 4), 3, np.int8))
-    assert model._itinf_map is None and model._itinf_quant["steps"] == [-6, 7]
+    assert model._itinf_grid["grid"].kind == "image" and model._itinf_grid["grid"].steps == [-6, 7]
     model.initialize_itinf(x, step_offsets=np.zeros((2, 4, 4), np.int8))
-    assert model._itinf_map is None and model._itinf_quant is None
+    assert model._itinf_grid is None
 
 
 # ---- 6. compress end to end ----------------------------------------------------------------------------------------------------

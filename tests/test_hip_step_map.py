@@ -344,10 +344,10 @@ def test_mapped_file(n, h, w, steps, dev, hyper_model):
     assert blob[:4] == b"SNTC" and blob[4] == 7
     hd = codec._parse(blob)
     assert hd["steps"] is None and hd["kmap"].dtype == np.int8 and (hd["kmap"] == K).all()
+    assert hd["grid"].kind == "map" and hd["grid"].kmap is hd["kmap"]
     # the symbols are the float32 rule on the encoder's y and mu; decompress = decode of them with the same offsets
     z, y = latents(model, x)
-    kd = torch.from_numpy(K.astype(np.int8)).to(dev)
-    zi, _, sym, ytid, hyper = codec._symbols(z, y, kmap=kd)
+    zi, _, sym, ytid, hyper = codec._symbols(z, y, ec.StepGrid("map", n, kmap=K.astype(np.int8)))
     c = y.shape[-1]
     flat = lambda t: t.cpu().numpy().reshape(n, -1, t.shape[-1])
     want_sym, want_tid, _ = np_map_symbols(flat(y), flat(hyper[..., :c]), flat(ec.scale_table_ids(hyper)), K.reshape(n, -1))

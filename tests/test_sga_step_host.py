@@ -85,7 +85,7 @@ def stand_in(**over):
         _distortion = "mse"
         _rd_lambda = 0.02
         factorized = False
-        _itinf_quant_of = Model._itinf_quant_of
+        _itinf_grid_of = Model._itinf_grid_of
         compress = Model.compress
         _check_step_arguments = Model._check_step_arguments
         _compress_itinf = Model._compress_itinf
@@ -153,10 +153,10 @@ def test_refusals_come_before_any_launch():
 def test_step_mode_quant_record():
     """Every index 0 and no rd_lambda is the path of before (None); anything else records the indexes and each image's lambda."""
     model = stand_in()
-    assert model._itinf_quant_of(2, None, None) is None
-    assert model._itinf_quant_of(2, 0, None) is None and model._itinf_quant_of(2, [0, 0], None) is None
-    q = model._itinf_quant_of(2, [0, 6], None)
+    assert model._itinf_grid_of(X.shape, None, None, None) is None
+    assert model._itinf_grid_of(X.shape, 0, None, None) is None and model._itinf_grid_of(X.shape, [0, 0], None, None) is None
+    q = model._itinf_grid_of(X.shape, [0, 6], None, None)
     from shallow_ntc_amd import entropy_coding as ec
-    assert q["steps"] == [0, 6] and q["lam"].tolist() == [0.02, 0.02 / ec.step_size(6) ** 2]
-    q = model._itinf_quant_of(2, None, 0.5)
-    assert q["steps"] == [0, 0] and q["lam"].tolist() == [0.5, 0.5]
+    assert q["grid"].kind == "image" and q["grid"].steps == [0, 6] and q["lam"].tolist() == [0.02, 0.02 / ec.step_size(6) ** 2]
+    q = model._itinf_grid_of(X.shape, None, 0.5, None)                # a lambda per image keeps the per-image kernels at step 0
+    assert q["grid"].kind == "image" and q["grid"].steps == [0, 0] and q["lam"].tolist() == [0.5, 0.5]

@@ -86,7 +86,7 @@ def map_stand_in(**over):
     """The stand-in of test_sga_step_host.py plus the host half of the map."""
     from shallow_ntc_amd.mshyper.models import Model
     stub = stand_in(**over)
-    type(stub)._itinf_map_of = Model._itinf_map_of
+    type(stub)._itinf_grid_of = Model._itinf_grid_of
     return stub
 
 

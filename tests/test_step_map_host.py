@@ -283,3 +283,41 @@ def test_selection_rule_with_map_bits():
     offs = i8([[[0, 0, 16, 16], [16, 0, 0, 0]]])
     assert ec.MAP_RECORD_BITS * ec.count_runs(offs)[0] == 8 * len(ec.pack_runs(ec.index_map([3], offs).reshape(1, -1))) == 24 * 3
     assert 8 * len(ec.pack_runs(ec.index_map([32], offs).reshape(1, -1))) == 24             # clipping merges runs: an upper bound
+
+
+# ------------------------------------------------------------------ the grid -----------------------------------------------
+def test_step_grid_routing_and_headers():
+    """``StepGrid.resolve`` is the one routing rule: nothing or all zeros -> unit, a map constant per image -> image at those
+    indexes (unit if all are 0), anything else -> map; ``pack`` / ``from_header`` keep the kind through the file.  Host only."""
+    from shallow_ntc_amd import entropy_coding as ec
+    G = ec.StepGrid
+    n, (_, _, _, _, h, w) = 2, shapes(64, 64)
+    zero, const, vary = np.zeros((n, h, w), np.int8), np.zeros((n, h, w), np.int8), np.zeros((n, h, w), np.int8)
+    const[1], vary[0, 0, 0] = 5, 1
+    for args in ((None, None), (0, None), ([0, 0], None), (None, zero), ([-5, 0], const + i8([5, -5]).reshape(n, 1, 1))):
+        g = G.resolve(*args, n, h, w)
+        assert g.kind == "unit" and g.steps is None and g.kmap is None and g.n == n, args
+    for args, want in ((([3, -3], None), [3, -3]), ((7, None), [7, 7]), ((1, const), [1, 6]), ((None, const), [0, 5]), (([30, 30], const), [30, 32])):
+        g = G.resolve(*args, n, h, w)
+        assert g.kind == "image" and g.steps == want and g.kmap is None, args
+    g = G.resolve([2, -40 + 8], vary, n, h, w)
+    assert g.kind == "map" and g.steps is None and g.kmap.dtype == np.int8 and (g.kmap == ec.index_map([2, -32], vary)).all()
+    assert G.image([0, 0]).kind == "image" and G.image([0, 0]).steps == [0, 0]         # what a per-image rd_lambda asks for
+    for bad in (([1], None), (33, None), (1.5, None), (None, zero[:1]), (None, zero.astype(np.float32)), (None, zero + 65)):
+        with pytest.raises(ValueError):
+            G.resolve(*bad, n, h, w)
+    # omega: the map's own weights; a unit or image grid broadcasts its indexes
+    assert (g.position_weights() == ec.position_weights(g.kmap)).all()
+    assert G.resolve(None, None, n).position_weights(h, w).tolist() == np.ones((n, h, w)).tolist()
+    assert (G.resolve([3, -3], None, n).position_weights(h, w) == ec.position_weights(ec.index_map([3, -3], zero))).all()
+    # the file keeps the kind: version byte 3 / 5 / 7, and the parsed header announces the same grid
+    case, payload = header_case(n, 64, 64)
+    fields = (0,) + tuple(case[k] for k in ("n", "H", "W", "dims", "sz", "sy", "lz", "ly", "zl", "yl"))
+    for grid, version in ((G.resolve(None, zero, n, h, w), 3), (G.resolve(1, const, n, h, w), 5), (g, 7)):
+        blob = grid.pack(*fields) + payload
+        assert blob[4] == version
+        assert blob == (ec.pack_v7(*fields, grid.kmap) if version == 7 else pack(case, grid.steps)) + payload
+        hd = (ec.parse_v7 if version == 7 else ec.parse_v3)(blob, "fp32", shapes)
+        back = G.from_header(hd)
+        assert back.kind == grid.kind and back.steps == grid.steps and back.n == n
+        assert (back.kmap is None) == (grid.kmap is None) and (grid.kmap is None or (back.kmap == grid.kmap).all())

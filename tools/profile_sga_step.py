@@ -140,7 +140,7 @@ def step_map(args):
         kw = dict(uniform=dict(step=-6), map=dict(step=-6, step_offsets=off))
         for which, model in models.items():
             model.initialize_itinf(x, **kw[which])
-        assert models["map"]._itinf_map is not None and models["uniform"]._itinf_map is None
+        assert models["map"]._itinf_grid["grid"].kind == "map" and models["uniform"]._itinf_grid["grid"].kind == "image"
         times = dict(uniform=[], map=[])
         for i in range(args.calls + 3):
             for which, model in models.items():
