@@ -539,7 +539,7 @@ __global__ void __launch_bounds__(256) tail_bwd_kernel(const float* __restrict__
       for (int i = 0; i < CH; ++i) {
         float m = 1.0f;
         if (act_kind == 3) m = xv[i] > 0.0f ? 1.0f : 0.0f;
-        if (act_kind == 4) m = xv[i] >= 0.0f ? 1.0f : 0.2f;
+        if (act_kind == 4) m = xv[i] > 0.0f ? 1.0f : 0.2f;
         dst[i] = g[i] * m;
       }
     }
