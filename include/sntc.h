@@ -593,6 +593,33 @@ int sntc_step_map_ladder_cost(const float* y, const float* mu, int n, int64_t hw
                               int ntables, int total_entries, const uint32_t* cost_q, uint64_t* cost, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Requantisation: the symbols of a coarser step from the symbols a file holds, without y and without pixels
+ *   (csrc/quant_step.hip, DESIGN.md 4.7 "transcode").  The reference quantises once, from y, with step 1
+ *   (mshyper/models.py:273-279) and has no second rate; here the source is what its decoder would hand the synthesis.  Per
+ *   element, at the source index k0 = src_map[image][position] and a destination index k1, with the three rules above and
+ *   nothing else:
+ *     y_hat0 = fmaf(lut[k0 + 32], (float)s0, mu)                        sntc_dequant_step_map's value, rounded to float32 once
+ *     s1     = (int)rintf((y_hat0 - mu) * lut[65 + k1 + 32])            sntc_step_map_symbols' symbol of it
+ *     t1     = clamp(base id - k1, 0, 63)
+ *   -- sntc_step_map_symbols / sntc_step_map_ladder_cost on the stored values of sntc_dequant_step_map, bit for bit, without
+ *   the y_hat tensor.  src_map / dst_map int8 [n][hw], clamped into [-32, 32] as every map; a unit or per-image grid is a
+ *   constant map.  lut float [2][65] as above.  Sizes and alignment as above (checked).
+ * ------------------------------------------------------------------------------------------------------- */
+/* k1 = dst_map[image][position].  Writes out_symbols int32 and out_table_ids uint16 in one pass.  symbols / mu / out_symbols
+ * 16-byte aligned, the id arrays 8-byte aligned (checked). */
+int sntc_step_requant_symbols(const int32_t* symbols, const float* mu, int n, int64_t hw, int c, int mu_stride,
+                              const uint16_t* base_ids, const int8_t* src_map, const int8_t* dst_map, const float* lut,
+                              int32_t* out_symbols, uint16_t* out_table_ids, void* stream);
+/* sntc_step_map_ladder_cost of the requantised symbols: candidate j (shift int32 [nsteps] on the device, 1 <= nsteps <= 16)
+ *   prices every element at k1 = clamp(clamp(src_map[image][p]) + shift[j], -32, 32).  cost uint64 [n][nsteps], zeroed by the
+ *   call, exact integer sums in 2^-16 bit.  One pass over symbols, mu, the ids and the map (about 10 bytes per element); no
+ *   y_hat or symbol tensor is written; the element-wise path for unaligned pointers, as there. */
+int sntc_step_requant_ladder_cost(const int32_t* symbols, const float* mu, int n, int64_t hw, int c, int mu_stride,
+                                  const uint16_t* base_ids, const int8_t* src_map, const float* lut, const int32_t* shift,
+                                  int nsteps, const uint32_t* meta, int ntables, int total_entries, const uint32_t* cost_q,
+                                  uint64_t* cost, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * The distortion side of the ladder (csrc/quant_step.hip, DESIGN.md 4.7 "quality target"): what every candidate step
  *   DECODES to, in one pass.  The reference decodes y_hat = round(y - mu) + mu once per evaluation (mshyper/models.py:273-279);
  *   here, per element and candidate j (1 <= nsteps <= 16), with the three rules above and nothing else,

@@ -162,6 +162,9 @@ SIGNATURES = {
     "sntc_dequant_step_map": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "sntc_step_map_ladder_cost": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int,
                                             C.c_int, _P, _P, _P]),
+    "sntc_step_requant_symbols": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "sntc_step_requant_ladder_cost": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int,
+                                                C.c_int, _P, _P, _P]),
     "sntc_step_ladder_dequant": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
     "sntc_step_map_ladder_dequant": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P]),
     "sntc_ssim_scale": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P]),

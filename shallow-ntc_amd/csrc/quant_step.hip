@@ -40,6 +40,15 @@
 // y and mu are read once per launch (8 bytes per element), every load feeds nsteps stores (4 nsteps bytes per element): with 16
 // candidates 64 bytes out per 8 in, the roof is HBM write bandwidth.  No atomics, no LDS; the MAP instances read the 65-entry
 // step table through the vector cache.
+//
+// Requantisation (REQ; transcoding a file to a coarser step without pixels, DESIGN.md 4.7 "transcode"): the source is not y but
+// the integers s0 a file holds at the indexes k0 of its own grid (a source map int8 [n][hw], clamped with map_index like every
+// map).  The difference the symbol rule rounds is then that of the value the decoder would feed the synthesis,
+//   d = step_diff(step_value(s0, mu, step[k0]), mu)          y_hat0 rounded to float32 once, as sntc_dequant_step_map stores it
+// and everything after d is the MAP instance unchanged: step_symbols_kernel<true, true> writes step_round(d, inv_step[k1]) and
+// step_table_id(base, k1) at k1 = a destination map's index, step_ladder_cost_kernel<true, ., ., true> prices candidate j at
+// k1 = map_index(k0 + shift[j]).  They equal the MAP entry points on the stored sntc_dequant_step_map values, bit for bit; no
+// y_hat tensor is written.
 #include <algorithm>
 #include "rans_common.h"
 #include "step_rules.h"
@@ -58,14 +67,20 @@ typedef int qs_i32x4 __attribute__((ext_vector_type(4)));
 typedef float qs_f32x4 __attribute__((ext_vector_type(4)));
 
 // grid (blocks per image, n); one thread = 4 consecutive channels of a position per pass (c % 4 == 0)
-template <bool MAP>
-__global__ void __launch_bounds__(256) step_symbols_kernel(const float* __restrict__ y, const float* __restrict__ mu,
+// REQ (with MAP): `src` holds a file's symbols (int32) in place of y, `src_map` the indexes they were quantised at; kmap is the
+// destination.
+template <bool MAP, bool REQ = false>
+__global__ void __launch_bounds__(256) step_symbols_kernel(const void* __restrict__ src, const float* __restrict__ mu,
                                                            const unsigned short* __restrict__ tid0, long long hw, int c, int mu_stride,
                                                            const float* __restrict__ inv_step, const int* __restrict__ shift,
+                                                           const signed char* __restrict__ src_map,
                                                            const signed char* __restrict__ kmap, const float* __restrict__ lut,
                                                            int* __restrict__ symbols, unsigned short* __restrict__ tid) {
+  static_assert(MAP || !REQ, "requantisation reads its grids from maps");
+  const float* y = static_cast<const float*>(src);
+  const int* s0 = static_cast<const int*>(src);
   const int img = blockIdx.y, c4 = c >> 2;
-  float inv = 1.0f;
+  float inv = 1.0f, st0 = 1.0f;
   int k = 0;
   if constexpr (!MAP) { inv = inv_step[img]; k = shift[img]; }
   const long long nvec = hw * c4, base = (long long)img * hw * c;
@@ -75,10 +90,18 @@ __global__ void __launch_bounds__(256) step_symbols_kernel(const float* __restri
     if constexpr (MAP) {
       k = map_index(kmap[(long long)img * hw + p]);
       inv = lut[kMapLut + k - kMapMin];
+      if constexpr (REQ) st0 = lut[map_index(src_map[(long long)img * hw + p]) - kMapMin];
     }
-    const qs_f32x4 yv = *reinterpret_cast<const qs_f32x4*>(y + base + i * 4);
     const qs_f32x4 m = *reinterpret_cast<const qs_f32x4*>(mu + ((long long)img * hw + p) * mu_stride + ch);
     const ushort4 t = *reinterpret_cast<const ushort4*>(tid0 + base + i * 4);
+    qs_f32x4 yv;
+    if constexpr (REQ) {
+      const qs_i32x4 sv = *reinterpret_cast<const qs_i32x4*>(s0 + base + i * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) yv[e] = step_value(sv[e], m[e], st0);
+    } else {
+      yv = *reinterpret_cast<const qs_f32x4*>(y + base + i * 4);
+    }
     qs_i32x4 s;
 #pragma unroll
     for (int e = 0; e < 4; ++e) s[e] = step_round(step_diff(yv[e], m[e]), inv);
@@ -143,9 +166,11 @@ __device__ __forceinline__ void next_unit(long long& p, int& r, int cu, int dq, 
 
 // nsteps <= kLadderMax candidates, uniform, their sums 64-bit per lane: inv_step / shift [nsteps], or (MAP) the bases kbase
 // [nsteps] added to the position's byte of offsets [n][hw].
-template <bool MAP, bool LDS, int V>
+// REQ (with MAP): `src` holds a file's symbols (int32) in place of y, `offsets` the indexes k0 they were quantised at (the source
+// map) and kbase the candidates' shifts; the step of k0 comes from row 0 of lut, staged beside the inverse steps.
+template <bool MAP, bool LDS, int V, bool REQ = false>
 __global__ void __launch_bounds__(kLadderThreads) step_ladder_cost_kernel(
-    const float* __restrict__ y, const float* __restrict__ mu, const unsigned short* __restrict__ tid0, long long hw, int c,
+    const void* __restrict__ src, const float* __restrict__ mu, const unsigned short* __restrict__ tid0, long long hw, int c,
     int mu_stride, const float* __restrict__ inv_step, const int* __restrict__ shift, const signed char* __restrict__ offsets,
     const float* __restrict__ lut, const int* __restrict__ kbase, int nsteps, RansTables T, const unsigned* __restrict__ cost_q, int dq,
     int dr, unsigned long long* __restrict__ cost) {
@@ -153,11 +178,20 @@ __global__ void __launch_bounds__(kLadderThreads) step_ladder_cost_kernel(
   __shared__ unsigned long long partial[kLadderThreads / 64][kLadderMax];
   const uint2* meta = T.meta;
   const unsigned* cq = cost_q;
+  static_assert(MAP || !REQ, "requantisation reads its grids from maps");
+  const float* y = static_cast<const float*>(src);
+  const int* s0 = static_cast<const int*>(src);
   const float* sinv = nullptr;
+  const float* sstep = nullptr;
   if constexpr (MAP) {
     __shared__ float row[kMapLut];
     if (threadIdx.x < kMapLut) row[threadIdx.x] = lut[kMapLut + threadIdx.x];
     sinv = row;
+  }
+  if constexpr (REQ) {
+    __shared__ float row0[kMapLut];
+    if (threadIdx.x < kMapLut) row0[threadIdx.x] = lut[threadIdx.x];
+    sstep = row0;
   }
   if constexpr (LDS) {
     uint2* m = reinterpret_cast<uint2*>(smem);
@@ -196,9 +230,21 @@ __global__ void __launch_bounds__(kLadderThreads) step_ladder_cost_kernel(
     const unsigned short* tp = tid0 + base + i * V;
     int off = 0;
     if constexpr (MAP) off = offsets[(long long)img * hw + p];
+    float st0 = 1.0f;
+    if constexpr (REQ) {
+      off = map_index(off);                                  // k0: the index the file's symbols were quantised at
+      st0 = sstep[off - kMapMin];
+    }
     if constexpr (V == 4) {
-      const qs_f32x4 yv = *reinterpret_cast<const qs_f32x4*>(yp);
       const qs_f32x4 mv = *reinterpret_cast<const qs_f32x4*>(mp);
+      qs_f32x4 yv;
+      if constexpr (REQ) {
+        const qs_i32x4 sv = *reinterpret_cast<const qs_i32x4*>(s0 + base + i * V);
+#pragma unroll
+        for (int e = 0; e < V; ++e) yv[e] = step_value(sv[e], mv[e], st0);
+      } else {
+        yv = *reinterpret_cast<const qs_f32x4*>(yp);
+      }
       const ushort4 tv = *reinterpret_cast<const ushort4*>(tp);
       const unsigned short ts[4] = {tv.x, tv.y, tv.z, tv.w};
 #pragma unroll
@@ -207,7 +253,11 @@ __global__ void __launch_bounds__(kLadderThreads) step_ladder_cost_kernel(
         t0[e] = ts[e];
       }
     } else {
-      d[0] = step_diff(yp[0], mp[0]);
+      const float m0 = mp[0];
+      float y0;
+      if constexpr (REQ) y0 = step_value(s0[base + i], m0, st0);
+      else y0 = yp[0];
+      d[0] = step_diff(y0, m0);
       t0[0] = tp[0];
     }
 #pragma unroll
@@ -347,22 +397,23 @@ static UnitGrid unit_grid(int64_t hw, int cu, int threads, int cap, int n) {
   return {grid, (int)(stride / cu), (int)(stride % cu)};
 }
 
-template <bool MAP, bool LDS, int V>
-static int launch_ladder_cost_instance(int lds, hipStream_t s, const float* y, const float* mu, const unsigned short* tid0, int n,
+template <bool MAP, bool LDS, int V, bool REQ>
+static int launch_ladder_cost_instance(int lds, hipStream_t s, const void* y, const float* mu, const unsigned short* tid0, int n,
                                        long long hw, int c, int mu_stride, const float* inv_step, const int* shift,
                                        const signed char* offsets, const float* lut, const int* kbase, int nsteps, const RansTables& T,
                                        const unsigned* cost_q, unsigned long long* cost) {
-  if (LDS) SNTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(step_ladder_cost_kernel<MAP, LDS, V>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  if (LDS) SNTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(step_ladder_cost_kernel<MAP, LDS, V, REQ>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   const UnitGrid g = unit_grid(hw, c / V, kLadderThreads, kLadderGrid, n);
-  hipLaunchKernelGGL((step_ladder_cost_kernel<MAP, LDS, V>), g.grid, dim3(kLadderThreads), LDS ? lds : 0, s, y, mu, tid0, hw, c, mu_stride,
+  hipLaunchKernelGGL((step_ladder_cost_kernel<MAP, LDS, V, REQ>), g.grid, dim3(kLadderThreads), LDS ? lds : 0, s, y, mu, tid0, hw, c, mu_stride,
                      inv_step, shift, offsets, lut, kbase, nsteps, T, cost_q, g.dq, g.dr, cost);
   SNTC_HIP(hipGetLastError());
   return SNTC_OK;
 }
 
-// inv_step / shift (per image) or offsets / lut / kbase (MAP), the others null; every check was made
-template <bool MAP>
-static int launch_ladder_cost(const float* y, const float* mu, int n, int64_t hw, int c, int mu_stride, const uint16_t* base_ids,
+// inv_step / shift (per image) or offsets / lut / kbase (MAP), the others null; REQ: y = the file's symbols, offsets = its map,
+// kbase = the shifts; every check was made
+template <bool MAP, bool REQ = false>
+static int launch_ladder_cost(const void* y, const float* mu, int n, int64_t hw, int c, int mu_stride, const uint16_t* base_ids,
                               const float* inv_step, const int* shift, const signed char* offsets, const float* lut, const int* kbase,
                               int nsteps, const uint32_t* meta, int ntables, int total_entries, const uint32_t* cost_q, uint64_t* cost,
                               hipStream_t s) {
@@ -371,8 +422,8 @@ static int launch_ladder_cost(const float* y, const float* mu, int n, int64_t hw
   const bool vec = aligned(y, 16) && aligned(mu, 16) && aligned(base_ids, 8);
   const long long tb = (long long)ntables * (long long)sizeof(uint2) + 4LL * total_entries;
   const bool lds = tb <= kLadderLdsLimit;
-  const auto launch = lds ? (vec ? launch_ladder_cost_instance<MAP, true, 4> : launch_ladder_cost_instance<MAP, true, 1>)
-                          : (vec ? launch_ladder_cost_instance<MAP, false, 4> : launch_ladder_cost_instance<MAP, false, 1>);
+  const auto launch = lds ? (vec ? launch_ladder_cost_instance<MAP, true, 4, REQ> : launch_ladder_cost_instance<MAP, true, 1, REQ>)
+                          : (vec ? launch_ladder_cost_instance<MAP, false, 4, REQ> : launch_ladder_cost_instance<MAP, false, 1, REQ>);
   return launch(lds ? (int)tb : 0, s, y, mu, base_ids, n, hw, c, mu_stride, inv_step, shift, offsets, lut, kbase, nsteps, T, cost_q,
                 reinterpret_cast<unsigned long long*>(cost));
 }
@@ -408,7 +459,7 @@ extern "C" int sntc_step_symbols(const float* y, const float* mu, int n, int64_t
   if (!aligned(y, 16) || !aligned(mu, 16) || !aligned(symbols, 16) || !aligned(base_ids, 8) || !aligned(table_ids, 8))
     return fail(SNTC_ERR_BAD_SHAPE, "sntc_step_symbols: y / mu / symbols must be 16-byte aligned, the id arrays 8-byte aligned");
   hipLaunchKernelGGL(step_symbols_kernel<false>, dim3(step_blocks(hw * (c / 4)), n), dim3(256), 0, (hipStream_t)stream, y, mu, base_ids,
-                     (long long)hw, c, mu_stride, inv_step, shift, nullptr, nullptr, symbols, table_ids);
+                     (long long)hw, c, mu_stride, inv_step, shift, nullptr, nullptr, nullptr, symbols, table_ids);
   SNTC_HIP(hipGetLastError());
   return SNTC_OK;
 }
@@ -422,7 +473,8 @@ extern "C" int sntc_step_map_symbols(const float* y, const float* mu, int n, int
   if (!aligned(y, 16) || !aligned(mu, 16) || !aligned(symbols, 16) || !aligned(base_ids, 8) || !aligned(table_ids, 8) || !aligned(lut, 4))
     return fail(SNTC_ERR_BAD_SHAPE, "sntc_step_map_symbols: y / mu / symbols must be 16-byte aligned, the id arrays 8-byte aligned");
   hipLaunchKernelGGL(step_symbols_kernel<true>, dim3(step_blocks(hw * (c / 4)), n), dim3(256), 0, (hipStream_t)stream, y, mu, base_ids,
-                     (long long)hw, c, mu_stride, nullptr, nullptr, reinterpret_cast<const signed char*>(kmap), lut, symbols, table_ids);
+                     (long long)hw, c, mu_stride, nullptr, nullptr, nullptr, reinterpret_cast<const signed char*>(kmap), lut, symbols,
+                     table_ids);
   SNTC_HIP(hipGetLastError());
   return SNTC_OK;
 }
@@ -505,6 +557,41 @@ extern "C" int sntc_step_map_ladder_cost(const float* y, const float* mu, int n,
   return launch_ladder_cost<true>(y, mu, n, hw, c, mu_stride, base_ids, nullptr, nullptr, reinterpret_cast<const signed char*>(offsets), lut,
                                   reinterpret_cast<const int*>(base), nsteps, meta, ntables, total_entries, cost_q, cost,
                                   (hipStream_t)stream);
+}
+
+extern "C" int sntc_step_requant_symbols(const int32_t* symbols, const float* mu, int n, int64_t hw, int c, int mu_stride,
+                                         const uint16_t* base_ids, const int8_t* src_map, const int8_t* dst_map, const float* lut,
+                                         int32_t* out_symbols, uint16_t* out_table_ids, void* stream) {
+  if (!symbols || !mu || !base_ids || !src_map || !dst_map || !lut || !out_symbols || !out_table_ids)
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_step_requant_symbols: null argument");
+  if (!step_sizes_ok(n, hw, c, mu_stride))
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_step_requant_symbols: bad sizes (1 <= n <= 65535, c % 4 == 0, mu_stride >= c, mu_stride % 4 == 0)");
+  if (!aligned(symbols, 16) || !aligned(mu, 16) || !aligned(out_symbols, 16) || !aligned(base_ids, 8) || !aligned(out_table_ids, 8) ||
+      !aligned(lut, 4))
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_step_requant_symbols: symbols / mu / out_symbols must be 16-byte aligned, the id arrays 8-byte aligned");
+  hipLaunchKernelGGL((step_symbols_kernel<true, true>), dim3(step_blocks(hw * (c / 4)), n), dim3(256), 0, (hipStream_t)stream, symbols, mu,
+                     base_ids, (long long)hw, c, mu_stride, nullptr, nullptr, reinterpret_cast<const signed char*>(src_map),
+                     reinterpret_cast<const signed char*>(dst_map), lut, out_symbols, out_table_ids);
+  SNTC_HIP(hipGetLastError());
+  return SNTC_OK;
+}
+
+extern "C" int sntc_step_requant_ladder_cost(const int32_t* symbols, const float* mu, int n, int64_t hw, int c, int mu_stride,
+                                             const uint16_t* base_ids, const int8_t* src_map, const float* lut, const int32_t* shift,
+                                             int nsteps, const uint32_t* meta, int ntables, int total_entries, const uint32_t* cost_q,
+                                             uint64_t* cost, void* stream) {
+  if (!symbols || !mu || !base_ids || !src_map || !lut || !shift || !meta || !cost_q || !cost)
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_step_requant_ladder_cost: null argument");
+  if (!step_sizes_ok(n, hw, c, mu_stride))
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_step_requant_ladder_cost: bad sizes (1 <= n <= 65535, c % 4 == 0, mu_stride >= c, mu_stride % 4 == 0)");
+  if (nsteps < 1 || nsteps > kLadderMax) return fail(SNTC_ERR_BAD_SHAPE, "sntc_step_requant_ladder_cost: 1 <= nsteps <= 16");
+  if (ntables <= kLadderTop || total_entries < 1)
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_step_requant_ladder_cost: the table set must hold the 64 tables of the scale ladder");
+  if (!aligned(symbols, 4) || !aligned(mu, 4) || !aligned(base_ids, 2) || !aligned(lut, 4) || !aligned(shift, 4) || !aligned(cost, 8))
+    return fail(SNTC_ERR_BAD_SHAPE, "sntc_step_requant_ladder_cost: misaligned argument");
+  return launch_ladder_cost<true, true>(symbols, mu, n, hw, c, mu_stride, base_ids, nullptr, nullptr,
+                                        reinterpret_cast<const signed char*>(src_map), lut, reinterpret_cast<const int*>(shift), nsteps, meta,
+                                        ntables, total_entries, cost_q, cost, (hipStream_t)stream);
 }
 
 extern "C" int sntc_step_ladder_dequant(const float* y, const float* mu, int n, int64_t hw, int c, int mu_stride, const float* inv_step,

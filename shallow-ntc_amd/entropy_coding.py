@@ -96,6 +96,30 @@ def check_steps(step, n):
     return ks
 
 
+def check_shifts(shift, n):
+    """``shift`` of ``transcode`` (an int, or a sequence of n ints: how many places up the ladder each image's file moves) -> list
+    of n ints in [0, STEP_MAX - STEP_MIN]; ValueError on anything else.  A negative shift is refused: the symbols of a finer
+    step are not in the file."""
+    if isinstance(shift, (int, np.integer)) and not isinstance(shift, bool):
+        ds = [int(shift)] * n
+    else:
+        try:
+            ds = list(shift)
+        except TypeError:
+            raise ValueError(f"shift must be an int or a sequence of {n} ints, not {shift!r}") from None
+        if len(ds) != n:
+            raise ValueError(f"{len(ds)} shifts for {n} images")
+        if not all(isinstance(d, (int, np.integer)) and not isinstance(d, bool) for d in ds):
+            raise ValueError(f"shifts must be ints (places on the scale ladder), not {ds!r}")
+        ds = [int(d) for d in ds]
+    for d in ds:
+        if d < 0:
+            raise ValueError(f"shift {d} is negative: a file holds the symbols of its own step, the finer ones are not in it")
+        if d > STEP_MAX - STEP_MIN:
+            raise ValueError(f"shift {d} outside [0, {STEP_MAX - STEP_MIN}]")
+    return ds
+
+
 def check_budgets(target_bpp, n):
     """``target_bpp`` (a number, or a sequence of n numbers) -> float64 [n]; ValueError on anything else."""
     t = np.asarray(target_bpp, np.float64)
@@ -739,6 +763,28 @@ class StepGrid:
             return cls("map", hd["n"], kmap=hd["kmap"])
         return cls("unit", hd["n"]) if hd["steps"] is None else cls.image(hd["steps"])
 
+    def indexes(self, h, w):
+        """The absolute ladder index of every latent position, int8 [n, h, w]: the map, or a unit / image grid broadcast over the
+        (h, w) positions it is given."""
+        if self.kind == "map":
+            return self.kmap
+        return index_map(self.steps or [0] * self.n, np.zeros((self.n, h, w), np.int8))
+
+    def shifted(self, d):
+        """The grid of clip(k + d_i, STEP_MIN, STEP_MAX): what a file on this grid becomes when image i is requantised ``d`` =
+        d_i >= 0 places up the ladder (``check_shifts``: an int or one per image).  A pure function; it collapses the way
+        ``resolve`` does -- a map that comes out constant per image is an image grid, all zeros the unit grid -- so the file
+        stays wire format 3, 5 or 7."""
+        ds = check_shifts(d, self.n)
+        if self.kind == "map":
+            kmap = index_map(ds, self.kmap)
+            ks = uniform_steps(kmap)
+            if ks is None:
+                return StepGrid("map", self.n, kmap=kmap)
+        else:
+            ks = [min(max(k + dd, STEP_MIN), STEP_MAX) for k, dd in zip(self.steps or [0] * self.n, ds)]
+        return StepGrid.image(ks) if any(ks) else StepGrid("unit", self.n)
+
     def on(self, device):
         """What the kernels read, on ``device`` (one small upload, kept): image -> ``step_tensors`` = (step, inv_step, shift);
         map -> (kmap int8 [n, h, w], ``cached_step_lut``); unit -> ()."""
@@ -857,6 +903,23 @@ def step_map_ladder_cost(y, hyper, base_ids, offsets, bases, tables: DeviceTable
         capi.call("sntc_step_map_ladder_cost", _p(y), _p(hyper), n, hw, c, hyper.shape[-1], _p(base_ids), _p(offsets), _p(lut),
                   _p(base_d[lo:lo + k]), k, _p(tables.meta), tables.ntables, tables.total, _p(tables.cost_q), _p(part), ops._stream())
     return _ladder_cost_chunks(y, len(bases), launch)
+
+
+def step_requant_ladder_cost(symbols, hyper, base_ids, src_map, shifts, tables: DeviceTables, lut=None):
+    """``step_map_ladder_cost`` of a file's symbols requantised up the ladder, without y: ``symbols`` int32 [n, h, w, c] were
+    quantised at the ladder indexes ``src_map`` int8 [n, h, w] (on the device); candidate j prices position p at
+    clip(src_map[image, p] + shifts[j], STEP_MIN, STEP_MAX) -- ``step_map_ladder_cost(dequant_step_map(symbols, ...), ...,
+    offsets=src_map, bases=shifts)``, exactly, in one pass per launch of at most ``LADDER_MAX`` candidates and without the y_hat
+    tensor (csrc/quant_step.hip).  -> int64 [n, len(shifts)] on the device, 2^-16 bit."""
+    shifts = check_shifts(list(shifts), len(shifts))
+    if not shifts:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "step_requant_ladder_cost: no candidate shift")
+    lut = cached_step_lut(symbols.device) if lut is None else lut
+    shifts_d = torch.tensor(shifts, dtype=torch.int32).to(symbols.device)
+
+    def launch(lo, k, part):
+        ops.step_requant_ladder_cost(symbols, hyper, base_ids, src_map, lut, shifts_d[lo:lo + k], tables, out=part)
+    return _ladder_cost_chunks(symbols, len(shifts), launch)
 
 
 def channel_table_ids(shape, device):
@@ -1068,24 +1131,35 @@ class Codec:
         return dict(n=n, H=H, W=W, z=z, y=y, sz=sz, sy=sy, lz=lz, ly=ly, zs=zs, zlen=zlen, ys=ys, ylen=ylen, grid=grid)
 
     def _finish(self, jobs):
-        """Launched jobs -> their blobs: the stream lengths of ALL jobs come back in one copy, the packed payloads in another."""
+        """Launched jobs -> their blobs: the stream lengths of ALL jobs come back in one copy, the packed payloads in another.
+        A job of ``transcode_many`` carries zlen = None: its z streams are not coded here but copied -- ``zl`` their lengths,
+        ``zbytes`` their words as the source blob holds them, ``dims`` the header's (C, Cz, hz, wz, h, w)."""
         m = self.m
-        lens_h = torch.cat([t for j in jobs for t in (j["zlen"], j["ylen"])]).cpu().numpy().astype(np.int64)     # read-back 1 of 2
+        lens_h = torch.cat([t for j in jobs for t in (j["zlen"], j["ylen"]) if t is not None]).cpu().numpy().astype(np.int64)   # read-back 1 of 2
         pays, o = [], 0
         for j in jobs:
-            nz, ny = j["zlen"].numel(), j["ylen"].numel()
-            j["zl"], j["yl"] = lens_h[o:o + nz], lens_h[o + nz:o + nz + ny]
-            o += nz + ny
-            pays += [rans_encode_finish(j["zs"], j["zlen"], j["zl"]), rans_encode_finish(j["ys"], j["ylen"], j["yl"])]
+            if j["zlen"] is not None:
+                nz = j["zlen"].numel()
+                j["zl"] = lens_h[o:o + nz]
+                o += nz
+                pays.append(rans_encode_finish(j["zs"], j["zlen"], j["zl"]))
+            ny = j["ylen"].numel()
+            j["yl"] = lens_h[o:o + ny]
+            o += ny
+            pays.append(rans_encode_finish(j["ys"], j["ylen"], j["yl"]))
         words = torch.cat(pays).cpu().numpy()                                                                    # read-back 2 of 2
         ops.check_conv_status()       # the copies synchronised the stream: a flagged stream-K launch raises here, not a wrong file
         out, o = [], 0
         for j in jobs:
-            z, y = j["z"], j["y"]
-            zw, yw = int(j["zl"].sum()), int(j["yl"].sum())
-            dims = (y.shape[-1], z.shape[-1], z.shape[1], z.shape[2], y.shape[1], y.shape[2])
+            copied = j["zlen"] is None
+            zw, yw = 0 if copied else int(j["zl"].sum()), int(j["yl"].sum())
+            if copied:
+                dims = j["dims"]
+            else:
+                z, y = j["z"], j["y"]
+                dims = (y.shape[-1], z.shape[-1], z.shape[1], z.shape[2], y.shape[1], y.shape[2])
             fields = (ARITH[m._precision], j["n"], j["H"], j["W"], dims, j["sz"], j["sy"], j["lz"], j["ly"], j["zl"], j["yl"])
-            out.append(j["grid"].pack(*fields) + words[o:o + zw + yw].tobytes())
+            out.append(j["grid"].pack(*fields) + (j["zbytes"] if copied else b"") + words[o:o + zw + yw].tobytes())
             o += zw + yw
         return out
 
@@ -1326,47 +1400,13 @@ class Codec:
             # one counter per entropy-decoding launch (the launch zeroes its own), ONE read-back for everything at the end: the
             # chain z symbols -> hyper-synthesis -> y symbols -> synthesis is enqueued without the host waiting in between
             bad = torch.zeros((2 * len(blobs),), dtype=torch.int32, device=dev)
-            # ONE upload for every blob's words and stream offsets (int64 offsets first, then the 16-bit words: both aligned)
-            offs = [np.concatenate([[0], np.cumsum(hd[k])]).astype(np.int64) for hd in heads for k in ("zl", "yl")]
-            words = [np.frombuffer(b, "<i2", hd["zw"] + hd["yw"], hd["pos"]) for b, hd in zip(blobs, heads)]
-            noff = sum(len(o) for o in offs)
-            host = np.empty(8 * noff + 2 * sum(len(w) for w in words), np.uint8)
-            host[:8 * noff].view(np.int64)[:] = np.concatenate(offs)
-            host[8 * noff:].view(np.int16)[:] = np.concatenate(words)
-            up = torch.from_numpy(host).to(dev)
-            off_d, word_d = up[:8 * noff].view(torch.int64), up[8 * noff:].view(torch.int16)
+            pay, offd = self._upload_streams(blobs, heads)
             # v5 / v7: every blob's step tensors or map go up here too, before anything is enqueued; they are read on the caller's
             # stream only
             grids = [hd["grid"] for hd in heads]
             for grid in grids:
                 grid.on(dev)
-            pay, offd = [], []
-            o = wpos = 0
-            for hd in heads:
-                nz, ny = len(hd["zl"]) + 1, len(hd["yl"]) + 1
-                offd.append((off_d[o:o + nz], off_d[o + nz:o + nz + ny]))
-                o += nz + ny
-                pay.append((word_d[wpos:wpos + hd["zw"]], word_d[wpos + hd["zw"]:wpos + hd["zw"] + hd["yw"]]))
-                wpos += hd["zw"] + hd["yw"]
-
-            def side_by_side(jobs):
-                outs = []
-                for st, job in zip(side, jobs):
-                    if st is not main:
-                        st.wait_stream(main)
-                    with torch.cuda.stream(st):
-                        outs.append(job())
-                for st, out in zip(side, outs):
-                    if st is not main:
-                        main.wait_stream(st)
-                        out.record_stream(main)
-                return outs
-
-            zis = side_by_side([
-                (lambda k=k, hd=hd: rans_decode(pay[k][0], hd["zl"], channel_table_ids((hd["n"], hd["hz"], hd["wz"], hd["cz"]), dev),
-                                                (hd["n"], hd["hz"], hd["wz"], hd["cz"]), self.z_tables, hd["sz"], hd["lz"], bad=bad[2 * k:2 * k + 1],
-                                                offsets=offd[k][0]))
-                for k, hd in enumerate(heads)])
+            zis = self._decode_hyper_latents(heads, pay, offd, bad, side, main)
             # From here on the blobs are PIPELINED, largest first: a blob's latents decode on its side stream while the caller's
             # stream runs the next blob's hyper-synthesis, and its synthesis runs while the later blobs' latents decode.  The first
             # blob's hyper-synthesis meets no decoding wave and keeps its stream-K launches; every convolution after it may run
@@ -1418,6 +1458,183 @@ class Codec:
                 raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {total} rANS streams did not terminate cleanly")
             ops.check_conv_status()       # wrong pixels never leave without an error
             return out
+
+    def _upload_streams(self, blobs, heads):
+        """ONE upload for every blob's words and stream offsets (int64 offsets first, then the 16-bit words: both aligned).
+        -> per blob (z words, y words) and (z offsets, y offsets), views of it on the device."""
+        dev = self.m.device
+        offs = [np.concatenate([[0], np.cumsum(hd[k])]).astype(np.int64) for hd in heads for k in ("zl", "yl")]
+        words = [np.frombuffer(b, "<i2", hd["zw"] + hd["yw"], hd["pos"]) for b, hd in zip(blobs, heads)]
+        noff = sum(len(o) for o in offs)
+        host = np.empty(8 * noff + 2 * sum(len(w) for w in words), np.uint8)
+        host[:8 * noff].view(np.int64)[:] = np.concatenate(offs)
+        host[8 * noff:].view(np.int16)[:] = np.concatenate(words)
+        up = torch.from_numpy(host).to(dev)
+        off_d, word_d = up[:8 * noff].view(torch.int64), up[8 * noff:].view(torch.int16)
+        pay, offd = [], []
+        o = wpos = 0
+        for hd in heads:
+            nz, ny = len(hd["zl"]) + 1, len(hd["yl"]) + 1
+            offd.append((off_d[o:o + nz], off_d[o + nz:o + nz + ny]))
+            o += nz + ny
+            pay.append((word_d[wpos:wpos + hd["zw"]], word_d[wpos + hd["zw"]:wpos + hd["zw"] + hd["yw"]]))
+            wpos += hd["zw"] + hd["yw"]
+        return pay, offd
+
+    def _decode_hyper_latents(self, heads, pay, offd, bad, side, main):
+        """The z symbols of every blob, each blob's launch on its own stream of ``side``, joined on ``main``; blob k's
+        bad-stream count goes to bad[2 k]."""
+        dev = self.m.device
+        outs = []
+        for k, (st, hd) in enumerate(zip(side, heads)):
+            if st is not main:
+                st.wait_stream(main)
+            with torch.cuda.stream(st):
+                shape = (hd["n"], hd["hz"], hd["wz"], hd["cz"])
+                outs.append(rans_decode(pay[k][0], hd["zl"], channel_table_ids(shape, dev), shape, self.z_tables, hd["sz"], hd["lz"],
+                                        bad=bad[2 * k:2 * k + 1], offsets=offd[k][0]))
+        for st, out in zip(side, outs):
+            if st is not main:
+                main.wait_stream(st)
+                out.record_stream(main)
+        return outs
+
+    def transcode(self, blob: bytes, shift=None, target_bpp=None) -> bytes:
+        """``transcode_many`` of one bitstream; ``shift`` / ``target_bpp``: a value or one per image.  ``last_report``: [its rows]."""
+        return self.transcode_many([blob], None if shift is None else [shift], None if target_bpp is None else [target_bpp])[0]
+
+    def transcode_many(self, blobs, shift=None, target_bpp=None):
+        """Bitstreams of this model -> the bitstreams of a coarser step, without pixels: image i of a blob moves d_i >= 0 places
+        up the scale ladder, every position from its index k0 to k1 = clip(k0 + d_i, STEP_MIN, STEP_MAX).  Per latent element
+        (csrc/quant_step.hip, one rule): y_hat0 = step_value(s0, mu, step[k0]) is what ``decompress`` would feed the
+        synthesis, s1 = step_round(step_diff(y_hat0, mu), inv_step[k1]) and t1 = step_table_id(base, k1) are coded.  The output is
+        ``compress_latents(z_hat, y_hat0, (H, W))`` on the grid k1, byte for byte: wire format 3, 5 or 7 (``StepGrid.shifted``),
+        the z streams and their header fields copied from the source.  The work is the front of ``decompress_many`` -- z decoded
+        side by side, the hyper-synthesis, y decoded with the source grid's tables, pipelined the same way -- then one
+        requantisation launch and the y coder per blob; no analysis, no synthesis.
+        Exactly one of ``shift`` / ``target_bpp``, each ONE value for every blob or a sequence with one entry per blob, an entry
+        being a value or one per image of that blob (``check_shifts`` / ``check_budgets``).  ``target_bpp``: per image the SMALLEST
+        d whose exact coded cost fits target_bpp H W -- ``select_steps`` over d = 0 .. STEP_MAX - min(k0) with the bits
+        ``compress(target_bpp=)`` compares (``rans_cost`` of z, the requantised y priced by ``step_requant_ladder_cost``, the flushed
+        lane states, 24 bits per run of a source map; header and length fields not counted), the top d and met = False where
+        none fits.  ``last_report``: per blob the rows of ``select_steps`` (step_chosen = d).  One read-back more than ``shift=``.
+        A corrupt source raises ``SntcError`` like ``decompress_many`` and yields no file."""
+        m = self.m
+        blobs = list(blobs)
+        if (shift is None) == (target_bpp is None):
+            raise ValueError("transcode: exactly one of shift and target_bpp")
+        require_fp32(m._precision, "transcode")
+        if not blobs:
+            return []
+        heads = [self._parse(b) for b in blobs]
+
+        def per_blob(value, check):
+            values = list(value) if isinstance(value, (list, tuple, np.ndarray)) else [value] * len(heads)
+            if len(values) != len(heads):
+                raise ValueError(f"transcode: {len(values)} entries for {len(heads)} bitstreams")
+            return [check(v, hd["n"]) for v, hd in zip(values, heads)]
+
+        grids = [hd["grid"] for hd in heads]
+        if shift is not None:
+            shifts = per_blob(shift, check_shifts)
+        else:
+            budgets = [b * float(hd["H"] * hd["W"]) for b, hd in zip(per_blob(target_bpp, check_budgets), heads)]
+        srcs = [g.indexes(hd["h"], hd["w"]) for g, hd in zip(grids, heads)]
+        dev = m.device
+        with torch.cuda.device(dev):
+            main = torch.cuda.current_stream()
+            side = self._side_streams(len(blobs)) if len(blobs) > 1 and not torch.cuda.is_current_stream_capturing() else [main] * len(blobs)
+            bad = torch.zeros((2 * len(blobs),), dtype=torch.int32, device=dev)
+            pay, offd = self._upload_streams(blobs, heads)
+            lut = cached_step_lut(dev)
+            # every blob's step tensors and source map go up here, before anything is enqueued (a map grid keeps its own copy)
+            src_d = [g.on(dev)[0] if g.kind == "map" else torch.from_numpy(s).to(dev) for g, s in zip(grids, srcs)]
+            for grid in grids:
+                grid.on(dev)
+            zis = self._decode_hyper_latents(heads, pay, offd, bad, side, main)
+            # as decompress_many: the blobs pipelined largest first, blob k's latents decoding on its stream while the caller's
+            # stream runs blob k + 1's hyper-synthesis; only the first hyper-synthesis keeps stream-K
+            piped = PIPELINE_BLOBS and len(heads) > 1 and side[0] is not main
+            order = sorted(range(len(heads)), key=lambda k: -(heads[k]["n"] * heads[k]["h"] * heads[k]["w"])) if piped else list(range(len(heads)))
+            hypers, bases, syms = [None] * len(heads), [None] * len(heads), [None] * len(heads)
+            for i, k in enumerate(order):
+                hd, st = heads[k], side[k]
+                with ops.static_schedules(piped and i > 0):
+                    hyper = m._hyper_synthesis(int_to_float(zis[k]))
+                if tuple(hyper.shape) != (hd["n"], hd["h"], hd["w"], 2 * hd["c"]):
+                    raise capi.SntcError(capi.ERR_BAD_SHAPE, f"hyper-synthesis output {tuple(hyper.shape)} does not match the latents "
+                                         f"{(hd['n'], hd['h'], hd['w'], hd['c'])}")
+                hypers[k], bases[k] = hyper, scale_table_ids(hyper)
+                tid = grids[k].table_ids(bases[k])
+                if st is not main:
+                    st.wait_stream(main)
+                with torch.cuda.stream(st):
+                    syms[k] = rans_decode(pay[k][1], hd["yl"], tid, (hd["n"], hd["h"], hd["w"], hd["c"]), self.y_tables, hd["sy"], hd["ly"],
+                                          bad=bad[2 * k + 1:2 * k + 2], offsets=offd[k][1])
+                if st is not main:
+                    tid.record_stream(st)
+            joined = set()
+
+            def join(k):                      # blob k's symbols on the caller's stream, once
+                if side[k] is not main and k not in joined:
+                    main.wait_stream(side[k])
+                    syms[k].record_stream(main)
+                joined.add(k)
+
+            if shift is None:
+                for k in order:
+                    join(k)
+                shifts = self._shift_control(heads, zis, syms, hypers, bases, srcs, src_d, budgets, bad)
+            jobs = [None] * len(heads)
+            for k in order:                   # blob k requantised and coded while the later blobs' latents still decode
+                hd = heads[k]
+                join(k)
+                out = grids[k].shifted(shifts[k])
+                dst = torch.from_numpy(np.ascontiguousarray(out.indexes(hd["h"], hd["w"]))).to(dev)
+                sym, tid = ops.step_requant_symbols(syms[k], hypers[k], bases[k], src_d[k], dst, lut)
+                ys, ylen = rans_encode_launch(sym, tid, self.y_tables, hd["sy"], hd["ly"])
+                z_end = hd["pos"] + 2 * hd["zw"]
+                jobs[k] = dict(n=hd["n"], H=hd["H"], W=hd["W"], sz=hd["sz"], sy=hd["sy"], lz=hd["lz"], ly=hd["ly"], zlen=None, zl=hd["zl"],
+                               zbytes=bytes(blobs[k][hd["pos"]:z_end]), dims=tuple(hd[f] for f in ("c", "cz", "hz", "wz", "h", "w")),
+                               ys=ys, ylen=ylen, grid=out)
+            out = self._finish(jobs)
+            nbad = int(bad.sum().item())
+            if nbad:
+                total = sum(hd["n"] * (hd["sz"] + hd["sy"]) for hd in heads)
+                raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {total} rANS streams did not terminate cleanly")
+            return out
+
+    def _shift_control(self, heads, zis, syms, hypers, bases, srcs, src_d, budgets, bad):
+        """The rate-control pass of ``transcode_many(target_bpp=...)``: every blob's shifts d = 0 .. STEP_MAX - min(k0) priced from
+        its decoded symbols (launches of at most ``LADDER_MAX`` candidates), ONE read-back for all blobs (the bad-stream counters
+        travel with it: a corrupt source raises here), then ``select_steps`` with the shifts as its steps -- the bits
+        ``_rate_control`` compares.  Fills ``last_report``; -> per blob the chosen shifts."""
+        dev = self.m.device
+        cands = [list(range(0, STEP_MAX - int(s.min()) + 1)) for s in srcs]
+        parts = [bad.to(torch.int64)]
+        for k, hd in enumerate(heads):
+            cost_z = rans_cost(zis[k], channel_table_ids(tuple(zis[k].shape), dev), self.z_tables)
+            cost_y = step_requant_ladder_cost(syms[k], hypers[k], bases[k], src_d[k], cands[k], self.y_tables)
+            parts += [cost_z, cost_y.reshape(-1)]
+        host = torch.cat(parts).cpu().numpy()                                                                    # the one read-back
+        nbad = int(host[:len(bad)].sum())
+        if nbad:
+            total = sum(hd["n"] * (hd["sz"] + hd["sy"]) for hd in heads)
+            raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {total} rANS streams did not terminate cleanly")
+        self.last_report, shifts, o = [], [], len(bad)
+        for k, hd in enumerate(heads):
+            n, S = hd["n"], len(cands[k])
+            cost_z, cost_y = host[o:o + n], host[o + n:o + n + n * S].reshape(n, S)
+            o += n + n * S
+            bits = (cost_z[:, None] + cost_y) / float(COST_UNIT) + float(self.flushed_bits(hd["H"], hd["W"]))
+            map_bits = MAP_RECORD_BITS * count_runs(srcs[k]) if hd["grid"].kind == "map" else None
+            report = select_steps(bits, budgets[k], cands[k], map_bits)
+            for i, r in enumerate(report):    # where nothing fits select_steps names the ladder's top: here that is the last shift
+                if not r["met"]:
+                    r.update(step_chosen=cands[k][-1], bits_predicted=float(bits[i, -1]) + r.get("map_bits", 0.0))
+            self.last_report.append(report)
+            shifts.append([r["step_chosen"] for r in report])
+        return shifts
 
     def _side_streams(self, count):
         return ops.side_streams(count, self.m.device)

@@ -24,7 +24,7 @@ from ..common.latent_rvs_lib import LatentRVCollection, UQLatentRV
 from ..common.latent_rvs_utils import sga_schedule_at_step
 from ..common.train_lib import Metrics
 from ..common.transforms import class_builder as transform_builder
-from ..entropy_coding import StepGrid, require_fp32
+from ..entropy_coding import StepGrid, check_shifts, require_fp32
 
 EMPTY_DICT = {}
 
@@ -991,6 +991,55 @@ class Model:
         """Several bitstreams -> their pixel batches; the entropy-decoding launches of all of them run side by side
         (entropy_coding.Codec.decompress_many).  Same pixels as one ``decompress`` per blob."""
         return self._get_codec().decompress_many(list(blobs))
+
+    def transcode(self, blob: bytes, shift=None, target_bpp=None) -> bytes:
+        """A bitstream of this model -> the bitstream of a coarser quantisation step, from the file alone: no pixels, no analysis,
+        no synthesis (entropy_coding.Codec.transcode_many, DESIGN.md 4.7 "transcode").  ``shift`` = d (an int, or one per image,
+        0 <= d <= STEP_MAX - STEP_MIN): every latent position moves from its ladder index k0 to clip(k0 + d, STEP_MIN, STEP_MAX);
+        the file's integers are dequantised as ``decompress`` would and requantised with the coarser step, the z stream is
+        copied.  The result is ``compress_latents(z_hat, y_hat0, (H, W), ...)`` of the source's decoded latents at the new
+        indexes, byte for byte, in wire format 3, 5 or 7.  It is NOT the file of ``compress(x, step=k0 + d)``: the second
+        rounding starts from y_hat0, not from y (DESIGN.md 4.7 has the measured price).  A negative shift is a ValueError: the
+        finer symbols are not in the file.  ``target_bpp`` (a number, or one per image): per image the smallest d whose exact
+        coded cost fits target_bpp H W, counted as ``compress(target_bpp=)`` counts; ``last_compress_report`` lists step_chosen
+        (= d), bits_predicted, budget_bits, met[, map_bits].  Exactly one of the two.  Mean-scale hyperprior models in precision
+        'fp32' only."""
+        self._check_transcode_arguments(shift, target_bpp)
+        codec = self._get_codec()
+        out = codec.transcode(blob, shift=shift, target_bpp=target_bpp)
+        if target_bpp is not None:
+            self.last_compress_report = codec.last_report[0]
+        return out
+
+    def transcode_many(self, blobs, shift=None, target_bpp=None):
+        """``transcode`` for several bitstreams -> theirs, in order, byte for byte what one ``transcode`` per blob returns; the
+        blobs' entropy-decoding launches run side by side as in ``decompress_many``.  ``shift`` / ``target_bpp``: one value for
+        every blob, or a sequence with one entry per blob (each a value, or one per image of that blob).  With ``target_bpp``
+        ``last_compress_report`` holds one report per blob."""
+        self._check_transcode_arguments(shift, target_bpp)
+        codec = self._get_codec()
+        out = codec.transcode_many(list(blobs), shift=shift, target_bpp=target_bpp)
+        if target_bpp is not None and out:
+            self.last_compress_report = codec.last_report
+        return out
+
+    def _check_transcode_arguments(self, shift, target_bpp):
+        """The refusals of ``transcode`` that need no bitstream; the per-image checks follow the header parse, before any launch."""
+        if (shift is None) == (target_bpp is None):
+            raise ValueError("transcode: exactly one of shift and target_bpp")
+        if self.factorized:
+            raise NotImplementedError("transcode: a factorized-prior model's per-channel tables would have to be rebuilt per step; "
+                                      "mean-scale hyperprior models only")
+        require_fp32(self._precision, "transcode(shift / target_bpp)")
+
+        def walk(v):                          # every shift, whatever the nesting per blob / per image: an int in range
+            if isinstance(v, (list, tuple, np.ndarray)):
+                for u in v:
+                    walk(u)
+            else:
+                check_shifts(v, 1)
+        if shift is not None:
+            walk(shift)
 
     # -- training (reference :375-383) -----------------------------------------------------------------------
     def train_step(self, image_batch):

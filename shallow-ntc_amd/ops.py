@@ -1351,6 +1351,47 @@ def dequant_step_map(symbols, hyper, kmap, lut):
     return y_hat
 
 
+def _check_requant_inputs(symbols, hyper, base_ids, src_map, lut, where):
+    n, hw, c, stride = _check_step_inputs(symbols, hyper, ())
+    _check_step_map(symbols, src_map, lut, where)
+    if symbols.dtype != torch.int32 or base_ids.dtype != torch.int16 or tuple(base_ids.shape) != tuple(symbols.shape) \
+            or not base_ids.is_contiguous():
+        raise ValueError(f"{where}: symbols int32, base_ids int16 (uint16 storage) like them")
+    return n, hw, c, stride
+
+
+def step_requant_symbols(symbols, hyper, base_ids, src_map, dst_map, lut):
+    """The symbols and table ids of a coarser grid from the symbols a file holds, without y (csrc/quant_step.hip): ``symbols``
+    int32 [n, h, w, c] were quantised at the ladder indexes ``src_map`` int8 [n, h, w]; at k0 = src_map, k1 = dst_map
+    -> (rint((fma(lut[0, k0 + 32], symbols, mu) - mu) * lut[1, k1 + 32]), clamp(base_ids - k1, 0, 63)) in one pass --
+    ``step_map_symbols(dequant_step_map(symbols, hyper, src_map, lut), hyper, base_ids, dst_map, lut)``, bit for bit."""
+    n, hw, c, stride = _check_requant_inputs(symbols, hyper, base_ids, src_map, lut, "step_requant_symbols")
+    _check_step_map(symbols, dst_map, lut, "step_requant_symbols")
+    sym = torch.empty_like(symbols)
+    tid = torch.empty_like(base_ids)
+    capi.call("sntc_step_requant_symbols", _ptr(symbols), _ptr(hyper), n, hw, c, stride, _ptr(base_ids), _ptr(src_map), _ptr(dst_map),
+              _ptr(lut), _ptr(sym), _ptr(tid), _stream())
+    return sym, tid
+
+
+def step_requant_ladder_cost(symbols, hyper, base_ids, src_map, lut, shifts, tables, out=None):
+    """What the coder would pay for ``step_requant_symbols`` at k1 = clip(src_map + shifts[j], -32, 32), for every candidate j of
+    ONE launch (``shifts`` int32 [nsteps] on the device, 1 <= nsteps <= 16), without forming a symbol or y_hat tensor:
+    -> int64 [n, nsteps] on the device, exact sums in 2^-16 bit.  ``tables``: the coder's device tables (meta, ntables, total,
+    cost_q: entropy_coding.DeviceTables).  ``out``: a caller's int64 [n, nsteps]."""
+    n, hw, c, stride = _check_requant_inputs(symbols, hyper, base_ids, src_map, lut, "step_requant_ladder_cost")
+    if not (isinstance(shifts, torch.Tensor) and shifts.dtype == torch.int32 and shifts.dim() == 1 and 1 <= shifts.numel() <= 16
+            and shifts.is_contiguous() and shifts.device == symbols.device):
+        raise ValueError("step_requant_ladder_cost: shifts int32 [1 .. 16] on the latents' device")
+    k = shifts.numel()
+    cost = torch.empty((n, k), dtype=torch.int64, device=symbols.device) if out is None else out
+    if cost.dtype != torch.int64 or tuple(cost.shape) != (n, k) or not cost.is_contiguous() or cost.device != symbols.device:
+        raise ValueError(f"step_requant_ladder_cost: out int64 {(n, k)}, contiguous, on the latents' device")
+    capi.call("sntc_step_requant_ladder_cost", _ptr(symbols), _ptr(hyper), n, hw, c, stride, _ptr(base_ids), _ptr(src_map), _ptr(lut),
+              _ptr(shifts), k, _ptr(tables.meta), tables.ntables, tables.total, _ptr(tables.cost_q), _ptr(cost), _stream())
+    return cost
+
+
 def _ladder_out(y, nsteps, out, where):
     """The output of the ladder-dequantisation kernels: float32 [nsteps, n, h, w, c], candidate-major (``out``: a caller's)."""
     shape = (nsteps,) + tuple(y.shape)
