@@ -638,6 +638,34 @@ int sntc_step_ladder_dequant(const float* y, const float* mu, int n, int64_t hw,
 int sntc_step_map_ladder_dequant(const float* y, const float* mu, int n, int64_t hw, int c, int mu_stride, const int8_t* offsets,
                                  const float* lut, const int32_t* base, int nsteps, float* y_hat, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The coded pixel residual layer (csrc/residual.hip, rule in csrc/residual_rules.h; wire format 8, DESIGN.md 4.7 "residual
+ *   layer").  The reference writes no file and bounds no pixel (mshyper/models.py:246-251, :313-317); this layer codes, over any
+ *   decoded base picture, the integers that bring every pixel within max_error = delta of the uint8 original (0: lossless).
+ *   Images are [n][h][w][c], 1 <= c <= 4, 1 <= n <= 65535, h w c < 2^31; base uint8 = the decoded base picture; x8 = the
+ *   original quantised as sntc_pixels_sse quantises it: (v + .5) 255, round half to even, saturate.  With m = 2 delta + 1, in
+ *   integers:
+ *     q  = sgn(x8 - base) ((|x8 - base| + delta) div m)                 |q| <= (255 + delta) div m
+ *     x~ = clip(base + q m, 0, 255)                                     |x8 - x~| <= delta
+ *     class(i, j, k) = level c + k,  level = 0 if a == 0 else min(7, floor(log2 a) + 1),
+ *     a = |base(i, min(j+1, w-1), k) - base(i, max(j-1, 0), k)| + |base(min(i+1, h-1), j, k) - base(max(i-1, 0), j, k)|
+ *   Refused with SNTC_ERR_BAD_SHAPE before any launch: a null pointer, max_error outside 0 .. 127, c outside 1 .. 4, a
+ *   non-positive size.  16-byte loads and stores where the pointers are aligned for them and h w c % 4 == 0, an element-wise
+ *   path with the same integers otherwise.  None of them allocates or synchronises.
+ * ------------------------------------------------------------------------------------------------------- */
+/* q int32 [n][h][w][c] and hist uint32 [n][8 c][511] (OVERWRITTEN): hist[image][class][q + 255] = how many values of that class
+ * took q.  The counts are integer atomics: exact whatever the launch geometry. */
+int sntc_residual_quantize(const float* x, const uint8_t* base, int n, int h, int w, int c, int max_error, int32_t* q,
+                           uint32_t* hist, void* stream);
+/* table_ids uint16 [n][h][w][c] = min(choice[image][class], 63), choice uint8 [n][8 c] on the device: the table the encoder
+ * chose per (image, class).  The encoder and the decoder call it on the same base picture. */
+int sntc_residual_table_ids(const uint8_t* base, const uint8_t* choice, int n, int h, int w, int c, uint16_t* table_ids,
+                            void* stream);
+/* out uint8 [n][h][w][c] = x~ for any int32 q; out_of_range int32 [1] on the device (zeroed by the call) counts the values with
+ * |q| > (255 + delta) div m, which no encoder writes: the decoder's corruption count, read where bad_streams is read. */
+int sntc_residual_apply(const uint8_t* base, const int32_t* q, int n, int h, int w, int c, int max_error, uint8_t* out,
+                        int32_t* out_of_range, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * SSIM / MS-SSIM statistics (eval-only quality metrics, reference mshyper/models.py:321-336 ->
  *   tf.image.ssim / tf.image.ssim_multiscale).  Images are float NHWC holding pixel

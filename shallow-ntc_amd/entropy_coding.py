@@ -25,6 +25,14 @@ Wire format v7 = v3 with version byte 7 and, between the header and the length f
   maximal runs in raster order, image after image, a record = i8 index | u16 run length 1 .. 65535 (``pack_runs``); a run never
   crosses an image boundary.  Written only when some image's map really varies: constant maps are the v5 / v3 blob of those
   indexes, byte for byte -- a file has one spelling.  Version 6 is not assigned and stays refused.
+Wire format v8 = a v3 / v5 / v7 blob wrapped in a coded pixel residual layer (csrc/residual.hip, DESIGN.md 4.7 "residual layer"):
+  b"SNTC" u16 version (low byte 8; high byte = the base's arithmetic tag) | u8 max_error (0 .. 127) | u8 levels (8) | u32 base_len |
+  the base file, complete and unchanged | u16 segments | u8 lanes | u8 0 | u8 choice[n * 24] | u32 len_words[n * segments] | payload.
+  The payload codes, per pixel value, q = sgn(r) ((|r| + max_error) div (2 max_error + 1)), r = the uint8 original - the decoded base
+  pixel, in the streams of v3 cut every 2^16 values, under ONE of the 64 y tables per (image, class) -- the table of smallest exact
+  coded cost, ``choice`` -- where the class of a value is its channel and the local activity of the decoded base picture, which the
+  decoder has.  The decoder adds q (2 max_error + 1) to the base and clips: every pixel within max_error of the original, the
+  original itself at 0.  ``split_residual(blob)[0]`` is the base file; a nested v8 base and a v4 base are refused.
 
 The factorized-prior model (factorized/models.py) has ONE latent and no hyper-synthesis: ``FactorizedCodec``, wire format v4
   b"SNTC" u16 version (low byte 4; high byte = the arithmetic tag, as above) | u16 n | u32 H | u32 W | u16 C | u16 h | u16 w |
@@ -1062,6 +1070,199 @@ def parse_v7(blob: bytes, precision, latent_shapes):
     return hd
 
 
+# -- the coded pixel residual layer, wire format 8 (csrc/residual.hip, DESIGN.md 4.7 "residual layer") ---------------------------
+VERSION_RESIDUAL = 8                      # a complete v3 / v5 / v7 blob + the coded residual of its decoded picture
+RESIDUAL_LEVELS, RESIDUAL_BINS, RESIDUAL_MAX_ERROR = 8, 511, 127
+RESIDUAL_CHANNELS = 3                     # the pictures a file holds are RGB: 8 levels x 3 channels = 24 classes per image
+RESIDUAL_ELEMS_PER_SEGMENT = 1 << 16      # one rANS stream per this many pixel values: 256 bytes of lane states = 0.03 bit / value,
+                                          # and 1024 decode steps per stream instead of the latents' 4096 (a step is a latency)
+RESIDUAL_MAX_ELEMS = (1 << 31) - 1        # values of one image the kernels index with 32 bits
+RESIDUAL_THREADS, RESIDUAL_VEC, RESIDUAL_GRID = 256, 4, 768   # csrc/residual.hip: a workgroup takes 256 units of 4 values (1 where
+                                          # a pointer or the image size is not a multiple of 4) per pass, about 768 workgroups a launch
+HEAD_V8 = "<HBBI"                         # version | max_error | levels | base_len
+TAIL_V8 = "<HBB"                          # segments | lanes | 0
+
+
+def check_max_error(max_error):
+    """``max_error`` of the public entry points -> int in [0, RESIDUAL_MAX_ERROR]; ValueError on anything else."""
+    if isinstance(max_error, bool) or not isinstance(max_error, (int, np.integer)) or not 0 <= int(max_error) <= RESIDUAL_MAX_ERROR:
+        raise ValueError(f"max_error must be an int in [0, {RESIDUAL_MAX_ERROR}], not {max_error!r}")
+    return int(max_error)
+
+
+def residual_streams(H, W, c=RESIDUAL_CHANNELS):
+    """(segments, lanes) of the residual streams of one H x W image: cut every ``RESIDUAL_ELEMS_PER_SEGMENT`` values."""
+    e = int(H) * int(W) * int(c)
+    segments = _segments(e, -(-e // RESIDUAL_ELEMS_PER_SEGMENT))
+    return segments, _lanes(-(-e // segments))
+
+
+def residual_prices(tabs):
+    """What q = -255 .. 255 costs under each of the first 64 tables of ``tabs``: int64 [64, 511] in 2^-16 bit, entry [t, q + 255] =
+    ``cost_table`` at the symbol the encoder codes (q - lo where that is a real symbol of the table, else ESCAPE)."""
+    q = np.arange(-(RESIDUAL_BINS // 2), RESIDUAL_BINS // 2 + 1, dtype=np.int64)
+    out = np.empty((NUM_SCALES, RESIDUAL_BINS), np.int64)
+    for t, (lo, f) in enumerate(tabs[:NUM_SCALES]):
+        cost = cost_table([(lo, f)]).astype(np.int64)
+        sym = q - int(lo)
+        out[t] = cost[np.where((sym < 0) | (sym >= len(f) - 1), len(f) - 1, sym)]
+    return out
+
+
+def residual_choice(hist, tabs):
+    """The table of every (image, class), a pure function: ``hist`` [n, classes, 511] = how many values of the class took
+    q = bin - 255 (``sntc_residual_quantize``), ``tabs`` the model's normal tables (``normal_tables()``).  Per (image, class) the
+    table with the smallest exact coded cost of the class's values (``residual_prices``: the encoder's ESCAPE rule), the lower
+    index on a tie, table 0 for an empty class.  -> (choice uint8 [n, classes], cost_q int64 [n] = the chosen tables' cost summed
+    over the image's classes, 2^-16 bit: what ``rans_cost`` returns for the image's q under the ids of the choice)."""
+    h = np.asarray(hist)
+    if h.ndim != 3 or h.shape[2] != RESIDUAL_BINS or not np.issubdtype(h.dtype, np.integer) or len(tabs) < NUM_SCALES:
+        raise ValueError(f"residual_choice: integer counts [n, classes, {RESIDUAL_BINS}] and the {NUM_SCALES} normal tables")
+    total = h.astype(np.int64) @ residual_prices(tabs).T             # [n, classes, 64], exact: integer matmul
+    choice = total.argmin(axis=2)                                    # the first minimum: the lower index on a tie
+    return choice.astype(np.uint8), total.min(axis=2).sum(axis=1).astype(np.int64)
+
+
+def _base_dims(base_blob):
+    """(version byte, arithmetic tag, n, H, W) of a hyperprior blob's fixed header; the blob is at least that long."""
+    word, n, H, W = struct.unpack_from("<HHII", base_blob, 4)
+    return word & 0xff, word >> 8, n, H, W
+
+
+def pack_v8(arith, max_error, base_blob, segments, lanes, choice, len_words) -> bytes:
+    """Everything of a v8 blob in front of its payload: b"SNTC" | u16 version (low byte 8, high byte the arithmetic tag) |
+    u8 max_error | u8 levels = 8 | u32 base_len | the base file, a complete v3 / v5 / v7 blob, unchanged | u16 segments | u8 lanes |
+    u8 0 | choice[n 8 3] | u32 len_words[n segments].  ValueError on what ``split_residual`` would refuse in the result."""
+    max_error = check_max_error(max_error)
+    base_blob = bytes(base_blob)
+    if len(base_blob) < 4 + struct.calcsize(HEAD_V3) or base_blob[:4] != MAGIC:
+        raise ValueError("pack_v8: the base is not an SNTC bitstream")
+    ver, tag, n, H, W = _base_dims(base_blob)
+    if ver not in (VERSION, VERSION_STEP, VERSION_MAP) or tag != arith:
+        raise ValueError(f"pack_v8: the base must be a v3 / v5 / v7 blob of the same arithmetic, not version {ver} tag {tag}")
+    choice = np.asarray(choice)
+    len_words = np.asarray(len_words, np.int64)
+    if choice.dtype != np.uint8 or choice.shape != (n, RESIDUAL_LEVELS * RESIDUAL_CHANNELS) or (choice.size and int(choice.max()) >= NUM_SCALES):
+        raise ValueError(f"pack_v8: choice uint8 {(n, RESIDUAL_LEVELS * RESIDUAL_CHANNELS)} of table indexes below {NUM_SCALES}")
+    if (segments, lanes) != residual_streams(H, W) or len(len_words) != n * segments:
+        raise ValueError("pack_v8: segment / lane / stream counts do not match the image size")
+    return MAGIC + struct.pack(HEAD_V8, VERSION_RESIDUAL | (arith << 8), max_error, RESIDUAL_LEVELS, len(base_blob)) + base_blob + \
+        struct.pack(TAIL_V8, segments, lanes, 0) + choice.tobytes() + len_words.astype("<u4").tobytes()
+
+
+def is_residual(blob) -> bool:
+    """Whether ``blob`` announces wire format 8 (its version byte; nothing else is checked)."""
+    return len(blob) > 4 and blob[:4] == MAGIC and blob[4] == VERSION_RESIDUAL
+
+
+def split_residual(blob):
+    """A v8 blob -> (its base file, a complete v3 / v5 / v7 blob, byte for byte; info = dict(arith, max_error, n, H, W, segments,
+    lanes, choice uint8 [n, 24], lens int64 [n segments], pos = payload offset, words)).  A pure host function: n, H, W come
+    from the base header, segments and lanes are recomputed from them and compared, the total length must match exactly; no
+    header field sizes an allocation.  Refused (SntcError): a choice byte >= 64, max_error > 127, levels != 8, a nested v8 base,
+    a v4 base, a short blob, a trailing byte.  The base's own checks are its decoder's (``parse_v3`` / ``parse_v7``)."""
+    bad = lambda what: capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream header: residual layer {what}")
+    blob = bytes(blob)
+    if blob[:4] != MAGIC:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "not an SNTC bitstream")
+    pos = 4 + struct.calcsize(HEAD_V8)
+    if len(blob) < pos:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+    word, max_error, levels, base_len = struct.unpack_from(HEAD_V8, blob, 4)
+    if word & 0xff != VERSION_RESIDUAL:
+        raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream version {word & 0xff}: split_residual reads version {VERSION_RESIDUAL}")
+    if max_error > RESIDUAL_MAX_ERROR:
+        raise bad(f"max_error {max_error} above {RESIDUAL_MAX_ERROR}")
+    if levels != RESIDUAL_LEVELS:
+        raise bad(f"of {levels} levels, not {RESIDUAL_LEVELS}")
+    if base_len < 4 + struct.calcsize(HEAD_V3) or len(blob) < pos + base_len + struct.calcsize(TAIL_V8):
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+    base_blob = blob[pos:pos + base_len]
+    pos += base_len
+    if base_blob[:4] != MAGIC:
+        raise bad("holds no SNTC bitstream as its base")
+    ver, tag, n, H, W = _base_dims(base_blob)
+    if ver not in (VERSION, VERSION_STEP, VERSION_MAP):
+        raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream header: residual layer over a version {ver} base; a base is version "
+                             f"{VERSION}, {VERSION_STEP} or {VERSION_MAP}")
+    if tag != word >> 8:
+        raise bad("and its base name different arithmetics")
+    if not (1 <= n <= Codec.MAX_IMAGES and 1 <= H <= Codec.MAX_SIDE and 1 <= W <= Codec.MAX_SIDE) or H * W * RESIDUAL_CHANNELS > RESIDUAL_MAX_ELEMS:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream header: implausible batch / image size n={n} H={H} W={W}")
+    segments, lanes, zero = struct.unpack_from(TAIL_V8, blob, pos)
+    pos += struct.calcsize(TAIL_V8)
+    if (segments, lanes) != residual_streams(H, W) or zero != 0:
+        raise bad("segment / lane counts do not match the image size")
+    ncls, ns = n * RESIDUAL_LEVELS * RESIDUAL_CHANNELS, n * segments
+    if len(blob) < pos + ncls + 4 * ns:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated")
+    choice = np.frombuffer(blob, np.uint8, ncls, pos).reshape(n, -1).copy()        # ncls bytes the blob was just found to hold
+    if int(choice.max()) >= NUM_SCALES:
+        raise bad(f"names table {int(choice.max())}; the model has {NUM_SCALES}")
+    lens = np.frombuffer(blob, "<u4", ns, pos + ncls).astype(np.int64)
+    pos += ncls + 4 * ns
+    words = int(lens.sum())
+    if len(blob) != pos + 2 * words:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, "bitstream truncated" if len(blob) < pos + 2 * words else
+                             "bitstream header: residual layer is followed by bytes it does not announce")
+    return base_blob, dict(arith=tag, max_error=max_error, n=n, H=H, W=W, segments=segments, lanes=lanes, choice=choice, lens=lens,
+                           pos=pos, words=words)
+
+
+def parse_v8(blob: bytes, precision, latent_shapes):
+    """``split_residual`` + the base's own parse against the decoding model (``parse_v3`` / ``parse_v7``: arithmetic, every
+    dimension recomputed).  -> (base_blob, the base's header dict, the layer's info dict)."""
+    base_blob, info = split_residual(blob)
+    mapped = base_blob[4] == VERSION_MAP
+    return base_blob, (parse_v7 if mapped else parse_v3)(base_blob, precision, latent_shapes), info
+
+
+def _check_residual_images(base, what, other=None, dtype=None):
+    """The checks the three kernels' wrappers share: ``base`` uint8 [n, h, w, c] contiguous; ``other`` of ``dtype`` like it."""
+    if not isinstance(base, torch.Tensor) or base.dtype != torch.uint8 or base.dim() != 4 or not base.is_contiguous():
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"{what}: base is a contiguous uint8 tensor [n, h, w, c]")
+    if other is not None and (not isinstance(other, torch.Tensor) or other.dtype != dtype or tuple(other.shape) != tuple(base.shape)
+                              or not other.is_contiguous() or other.device != base.device):
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"{what}: a contiguous {dtype} tensor of base's shape {tuple(base.shape)} on its device")
+
+
+def residual_quantize(x, base, max_error):
+    """``sntc_residual_quantize``: x float32 [n, h, w, c] (image values, -0.5 .. 0.5), base uint8 like it -> (q int32 like x,
+    hist int32 storage of uint32 [n, 8 c, 511]: the counts of q + 255 per (image, class)).  No host synchronisation."""
+    _check_residual_images(base, "residual_quantize", x, torch.float32)
+    n, h, w, c = base.shape
+    q = torch.empty(tuple(base.shape), dtype=torch.int32, device=base.device)
+    hist = torch.empty((n, RESIDUAL_LEVELS * c, RESIDUAL_BINS), dtype=torch.int32, device=base.device)
+    capi.call("sntc_residual_quantize", _p(x), _p(base), n, h, w, c, int(max_error), _p(q), _p(hist), ops._stream())
+    return q, hist
+
+
+def residual_table_ids(base, choice):
+    """``sntc_residual_table_ids``: base uint8 [n, h, w, c], choice uint8 [n, 8 c] on its device -> ids int16 storage of uint16
+    like base: the chosen table of every value's class."""
+    _check_residual_images(base, "residual_table_ids")
+    n, h, w, c = base.shape
+    if not isinstance(choice, torch.Tensor) or choice.dtype != torch.uint8 or tuple(choice.shape) != (n, RESIDUAL_LEVELS * c) \
+            or not choice.is_contiguous() or choice.device != base.device:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"residual_table_ids: choice uint8 {(n, RESIDUAL_LEVELS * c)} on base's device")
+    ids = torch.empty(tuple(base.shape), dtype=torch.int16, device=base.device)
+    capi.call("sntc_residual_table_ids", _p(base), _p(choice), n, h, w, c, _p(ids), ops._stream())
+    return ids
+
+
+def residual_apply(base, q, max_error, count=None):
+    """``sntc_residual_apply``: base uint8 [n, h, w, c], q int32 like it -> (x~ uint8 like base, count int32 [1] on the device:
+    the values of q no encoder writes at this ``max_error``; ``count``: where to leave it, zeroed by the call).  No host
+    synchronisation."""
+    _check_residual_images(base, "residual_apply", q, torch.int32)
+    n, h, w, c = base.shape
+    if count is None:
+        count = torch.empty((1,), dtype=torch.int32, device=base.device)
+    out = torch.empty_like(base)
+    capi.call("sntc_residual_apply", _p(base), _p(q), n, h, w, c, int(max_error), _p(out), _p(count), ops._stream())
+    return out, count
+
+
 class Codec:
     """compress / decompress for a mean-scale hyperprior ``Model``."""
 
@@ -1392,6 +1593,15 @@ class Codec:
         m = self.m
         if not blobs:
             return []
+        # wire format 8: the base file inside goes through the pipeline below unchanged, its residual layer follows the syntheses
+        layers = [None] * len(blobs)
+        if any(is_residual(b) for b in blobs):
+            blobs = list(blobs)
+            for k, b in enumerate(blobs):
+                if is_residual(b):
+                    blobs[k], layers[k] = split_residual(b)
+                    layers[k]["blob"] = b
+        nlayers = sum(l is not None for l in layers)
         heads = [self._parse(b) for b in blobs]
         dev = m.device
         with torch.cuda.device(dev):
@@ -1399,7 +1609,8 @@ class Codec:
             side = self._side_streams(len(blobs)) if len(blobs) > 1 and not torch.cuda.is_current_stream_capturing() else [main] * len(blobs)
             # one counter per entropy-decoding launch (the launch zeroes its own), ONE read-back for everything at the end: the
             # chain z symbols -> hyper-synthesis -> y symbols -> synthesis is enqueued without the host waiting in between
-            bad = torch.zeros((2 * len(blobs),), dtype=torch.int32, device=dev)
+            # (a residual layer adds two behind the others: its streams', and the out-of-range count of sntc_residual_apply)
+            bad = torch.zeros((2 * (len(blobs) + nlayers),), dtype=torch.int32, device=dev)
             pay, offd = self._upload_streams(blobs, heads)
             # v5 / v7: every blob's step tensors or map go up here too, before anything is enqueued; they are read on the caller's
             # stream only
@@ -1452,12 +1663,138 @@ class Codec:
                 with ops.static_schedules(piped and i + 1 < len(order)):
                     y_hat = grids[k].dequant(syms[k], hypers[k], m._synthesis.takes_s3(hd["h"], hd["w"]))
                     out[k] = m._pixels(y_hat, (hd["H"], hd["W"]))
+            if nlayers:
+                self._apply_layers(layers, out, bad[2 * len(blobs):], main)
             nbad = int(bad.sum().item())                           # synchronises the stream
             if nbad:
                 total = sum(hd["n"] * (hd["sz"] + hd["sy"]) for hd in heads)
+                if nlayers:
+                    counts = bad.cpu().numpy()
+                    nres = int(counts[2 * len(blobs) + 1::2].sum())
+                    total += sum(l["n"] * l["segments"] for l in layers if l is not None)
+                    raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad - nres} of {total} rANS streams did not terminate "
+                                         f"cleanly, {nres} residual values lie outside what an encoder writes")
                 raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {total} rANS streams did not terminate cleanly")
             ops.check_conv_status()       # wrong pixels never leave without an error
             return out
+
+    def _apply_layers(self, layers, out, bad, main):
+        """The residual layers of ``decompress_many``: ``layers[k]`` = ``split_residual``'s info of blob k or None, ``out[k]`` its
+        decoded base picture, already enqueued on ``main``.  ONE upload for every layer's words, stream offsets and choices; per
+        layer, on a pooled side stream, ``residual_table_ids`` -> ``rans_decode`` -> ``residual_apply`` replaces out[k]; layer j's
+        bad-stream count goes to bad[2 j], its out-of-range count to bad[2 j + 1].  The layers start after the last synthesis
+        was enqueued: their decoding waves run side by side with each other, never beside a stream-K convolution."""
+        dev = self.m.device
+        ks = [k for k, l in enumerate(layers) if l is not None]
+        offs = [np.concatenate([[0], np.cumsum(layers[k]["lens"])]).astype(np.int64) for k in ks]
+        noff, nword = sum(len(o) for o in offs), sum(layers[k]["words"] for k in ks)
+        host = np.empty(8 * noff + 2 * nword + sum(layers[k]["choice"].size for k in ks), np.uint8)
+        host[:8 * noff].view(np.int64)[:] = np.concatenate(offs)
+        host[8 * noff:8 * noff + 2 * nword].view(np.int16)[:] = np.concatenate([np.frombuffer(layers[k]["blob"], "<i2", layers[k]["words"],
+                                                                                              layers[k]["pos"]) for k in ks])
+        host[8 * noff + 2 * nword:] = np.concatenate([layers[k]["choice"].reshape(-1) for k in ks])
+        up = torch.from_numpy(host).to(dev)
+        off_d, word_d, choice_d = up[:8 * noff].view(torch.int64), up[8 * noff:8 * noff + 2 * nword].view(torch.int16), up[8 * noff + 2 * nword:]
+        side = [main] * len(ks) if torch.cuda.is_current_stream_capturing() else self._side_streams(len(ks))
+        o = wpos = cpos = 0
+        for j, (k, st) in enumerate(zip(ks, side)):
+            l, base = layers[k], out[k]
+            shape = (l["n"], l["H"], l["W"], RESIDUAL_CHANNELS)
+            if tuple(base.shape) != shape:
+                raise capi.SntcError(capi.ERR_BAD_SHAPE, f"decoded base picture {tuple(base.shape)} does not match the residual layer's {shape}")
+            choice = choice_d[cpos:cpos + l["choice"].size].view(l["n"], -1)
+            if st is not main:
+                st.wait_stream(main)
+            with torch.cuda.stream(st):
+                ids = residual_table_ids(base, choice)
+                q = rans_decode(word_d[wpos:wpos + l["words"]], l["lens"], ids, shape, self.y_tables, l["segments"], l["lanes"],
+                                bad=bad[2 * j:2 * j + 1], offsets=off_d[o:o + len(offs[j])])
+                out[k], _ = residual_apply(base, q, l["max_error"], count=bad[2 * j + 1:2 * j + 2])
+            if st is not main:
+                for t in (base, up):
+                    t.record_stream(st)
+            o += len(offs[j])
+            wpos += l["words"]
+            cpos += l["choice"].size
+        for k, st in zip(ks, side):
+            if st is not main:
+                main.wait_stream(st)
+                out[k].record_stream(main)
+
+    def _refuse_layered(self, blobs, what):
+        for b in blobs:
+            if is_residual(b):
+                raise ValueError(f"{what}: the bitstream carries a residual layer (wire format {VERSION_RESIDUAL}); take its base file with "
+                                 "entropy_coding.split_residual(blob)[0] and add a layer to the result with add_residual")
+
+    def _layer(self, base_blob, base, x, delta):
+        """The residual layer of ``x`` float32 [n, H, W, 3] over the decoded picture ``base`` of ``base_blob`` -> the v8 blob:
+        ``residual_quantize``, ONE read-back of the histogram, ``residual_choice``, ``residual_table_ids``, ``rans_encode`` with the
+        model's y tables, ``pack_v8``.  Fills ``last_residual``."""
+        _, H, W, c = base.shape
+        if tuple(x.shape) != tuple(base.shape) or x.dtype != torch.float32 or c != RESIDUAL_CHANNELS:
+            raise ValueError(f"add_residual: images {tuple(x.shape)} are not the {tuple(base.shape)} the bitstream decodes to")
+        if H * W * c > RESIDUAL_MAX_ELEMS:
+            raise ValueError(f"add_residual: an image of more than {RESIDUAL_MAX_ELEMS} values")
+        q, hist = residual_quantize(x, base, delta)
+        hist_h = hist.cpu().numpy().view(np.uint32)                                                     # the one read-back of the histogram
+        choice, cost_q = residual_choice(hist_h, self.y_tables.host)
+        ids = residual_table_ids(base, torch.from_numpy(choice).to(base.device))
+        segments, lanes = residual_streams(H, W)
+        payload, lens = rans_encode(q, ids, self.y_tables, segments, lanes)
+        words = payload.cpu().numpy()
+        ops.check_conv_status()
+        self.last_residual = dict(max_error=delta, choice=choice, cost_q=cost_q, hist=hist_h,
+                                  bits_predicted=cost_q / float(COST_UNIT) + 32.0 * segments * lanes)
+        return pack_v8(ARITH[self.m._precision], delta, base_blob, segments, lanes, choice, lens) + words.tobytes()
+
+    def add_residual(self, blob: bytes, x, max_error) -> bytes:
+        """A v3 / v5 / v7 bitstream of this model and the images it was made from -> the v8 bitstream whose decoded pixels are
+        within ``max_error`` (an int, 0 .. 127; 0: lossless) of x quantised to uint8, every one of them: the base file unchanged,
+        then the coded residual q = sgn(r) ((|r| + max_error) div (2 max_error + 1)), r = x8 - the base's decoded pixel
+        (csrc/residual_rules.h), under one of the model's 64 normal tables per (image, class), chosen by exact coded cost.
+        ``split_residual(result)[0] == blob``.  A v8 ``blob`` is a ValueError.  ``last_residual``: max_error, choice, cost_q,
+        bits_predicted per image, and hist, the histogram the choice was made from."""
+        m = self.m
+        delta = check_max_error(max_error)
+        require_fp32(m._precision, "the residual layer")
+        self._refuse_layered([blob], "add_residual")
+        x = self._layer_images(blob, x, "add_residual")
+        with torch.cuda.device(m.device):
+            return self._layer(bytes(blob), self.decompress(blob), x, delta)
+
+    def _layer_images(self, blob, x, what):
+        """``x`` of ``add_residual`` / ``residual_bits`` on the device, checked against the header of ``blob`` before any launch."""
+        x = self.m._as_device_images(x)
+        hd = self._parse(blob)
+        shape = (hd["n"], hd["H"], hd["W"], RESIDUAL_CHANNELS)
+        if tuple(x.shape) != shape or x.dtype != torch.float32:
+            raise ValueError(f"{what}: float32 images {tuple(x.shape)} are not the {shape} the bitstream decodes to")
+        if hd["H"] * hd["W"] * RESIDUAL_CHANNELS > RESIDUAL_MAX_ELEMS:
+            raise ValueError(f"{what}: an image of more than {RESIDUAL_MAX_ELEMS} values")
+        return x
+
+    def residual_bits(self, x, blob: bytes, max_error):
+        """What the residual layer of ``add_residual(blob, x, d)`` would pay per image, without coding anything: ``max_error`` an
+        int -> float64 [n], a list of ints -> [n, len].  The exact coded cost of the chosen tables (``residual_choice``) / 65536 +
+        32 bits per flushed lane state; the coder's renormalisation slack, the choice bytes and the length fields are not in it.
+        One decode of the base, one quantisation launch per value, ONE read-back."""
+        m = self.m
+        many = not isinstance(max_error, (int, np.integer)) or isinstance(max_error, bool)
+        deltas = [check_max_error(d) for d in (max_error if many else [max_error])]
+        if not deltas:
+            raise ValueError("residual_bits: no max_error")
+        require_fp32(m._precision, "the residual layer")
+        self._refuse_layered([blob], "residual_bits")
+        x = m._as_device_images(x)
+        with torch.cuda.device(m.device):
+            base = self.decompress(blob)
+            if tuple(x.shape) != tuple(base.shape) or x.dtype != torch.float32:
+                raise ValueError(f"residual_bits: images {tuple(x.shape)} are not the {tuple(base.shape)} the bitstream decodes to")
+            hists = torch.stack([residual_quantize(x, base, d)[1] for d in deltas]).cpu().numpy().view(np.uint32)      # the one read-back
+        segments, lanes = residual_streams(base.shape[1], base.shape[2])
+        bits = np.stack([residual_choice(h, self.y_tables.host)[1] / float(COST_UNIT) + 32.0 * segments * lanes for h in hists], axis=1)
+        return bits if many else bits[:, 0]
 
     def _upload_streams(self, blobs, heads):
         """ONE upload for every blob's words and stream offsets (int64 offsets first, then the 16-bit words: both aligned).
@@ -1524,6 +1861,7 @@ class Codec:
         if (shift is None) == (target_bpp is None):
             raise ValueError("transcode: exactly one of shift and target_bpp")
         require_fp32(m._precision, "transcode")
+        self._refuse_layered(blobs, "transcode")
         if not blobs:
             return []
         heads = [self._parse(b) for b in blobs]

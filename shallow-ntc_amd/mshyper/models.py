@@ -688,7 +688,7 @@ class Model:
             self._codec = Codec(self)
         return self._codec
 
-    def compress(self, x, itinf=None, step=None, target_bpp=None, step_offsets=None, target_psnr=None) -> bytes:
+    def compress(self, x, itinf=None, step=None, target_bpp=None, step_offsets=None, target_psnr=None, max_error=None) -> bytes:
         """Images -> self-contained bitstream (rANS over the integer CDF tables of both entropy models).
         ``itinf`` = dict(steps, seed=0, check_every=None): refine the latents of THESE images by SGA iterative inference first
         (``initialize_itinf`` + ``steps`` x ``itinf_train_step(x, seed=seed, fetch=False)`` under the model's own tau / learning-rate
@@ -744,19 +744,68 @@ class Model:
         ``target_bpp`` compares; the file is that of ``step=`` the chosen indexes, byte for byte (with ``step_offsets`` the
         candidates are bases of the map and map_bits is counted, as for ``target_bpp``).  ``last_compress_report`` lists
         step_chosen, bits_predicted, sse_predicted, psnr_predicted, sse_budget, met.  Excludes ``step``, ``target_bpp`` and
-        ``itinf``; inside the ``itinf`` dict it is not implemented."""
+        ``itinf``; inside the ``itinf`` dict it is not implemented.
+        ``max_error`` (an int, 0 .. 127): a hard bound on every decoded pixel -- the file of the other arguments, whatever they
+        are (``itinf`` included), wrapped in a coded residual layer (wire format 8, ``add_residual``): ``decompress`` then gives
+        pixels within max_error of x quantised to uint8, that picture itself at 0.  Byte for byte
+        ``add_residual(compress(x, ...), x, max_error)``.  ``last_compress_report`` gains, per image, max_error,
+        residual_bits_predicted and residual_tables (a plain ``compress(x, max_error=d)`` reports just these).  Mean-scale
+        hyperprior models in precision 'fp32' only."""
+        if max_error is not None:
+            self._check_residual_arguments("compress", max_error)
         self._check_step_arguments("compress", step, target_bpp, itinf, step_offsets, target_psnr=target_psnr)
         if itinf is not None:
             if "target_psnr" in itinf:
                 raise ValueError("compress: target_psnr is not implemented inside itinf")
-            return self._compress_itinf(x, **itinf)
-        if step is None and target_bpp is None and step_offsets is None and target_psnr is None:
-            return self._get_codec().compress(x)
+            blob = self._compress_itinf(x, **itinf)
+        elif step is None and target_bpp is None and step_offsets is None and target_psnr is None:
+            blob = self._get_codec().compress(x)
+        else:
+            codec = self._get_codec()
+            blob = codec.compress(x, step=step, target_bpp=target_bpp, step_offsets=step_offsets, target_psnr=target_psnr)
+            if target_bpp is not None or target_psnr is not None:
+                self.last_compress_report = codec.last_report
+        if max_error is None:
+            return blob
+        reported = itinf is not None or target_bpp is not None or target_psnr is not None
+        return self._add_residual(blob, x, max_error, self.last_compress_report if reported else None)
+
+    def _check_residual_arguments(self, where, max_error):
+        """The refusals of the residual layer that need no image: every one before any launch."""
+        from ..entropy_coding import check_max_error
+        if self.factorized:
+            raise NotImplementedError(f"{where}(max_error): the residual layer codes with the scale ladder's normal tables; mean-scale "
+                                      "hyperprior models only")
+        for d in (max_error if isinstance(max_error, (list, tuple, np.ndarray)) else [max_error]):
+            check_max_error(d)
+        require_fp32(self._precision, f"{where}(max_error)")
+
+    def _add_residual(self, blob, x, max_error, report):
         codec = self._get_codec()
-        blob = codec.compress(x, step=step, target_bpp=target_bpp, step_offsets=step_offsets, target_psnr=target_psnr)
-        if target_bpp is not None or target_psnr is not None:
-            self.last_compress_report = codec.last_report
-        return blob
+        out = codec.add_residual(blob, x, max_error)
+        last = codec.last_residual
+        rows = [dict() for _ in last["cost_q"]] if report is None else report
+        for i, r in enumerate(rows):
+            r.update(max_error=last["max_error"], residual_bits_predicted=float(last["bits_predicted"][i]),
+                     residual_tables=[int(t) for t in last["choice"][i]])
+        self.last_compress_report = rows
+        return out
+
+    def add_residual(self, blob: bytes, x, max_error) -> bytes:
+        """A v3 / v5 / v7 bitstream of this model and the images it was made from -> the same file wrapped in a coded residual
+        layer (wire format 8; entropy_coding.Codec.add_residual, DESIGN.md 4.7 "residual layer"): every decoded pixel is then
+        within ``max_error`` (0 .. 127; 0: lossless) of x quantised to uint8.  A blob that already carries a layer is a
+        ValueError: ``entropy_coding.split_residual(blob)[0]`` is its base file.  ``last_compress_report``: per image max_error,
+        residual_bits_predicted, residual_tables."""
+        self._check_residual_arguments("add_residual", max_error)
+        return self._add_residual(blob, x, max_error, None)
+
+    def residual_bits(self, x, blob: bytes, max_error):
+        """What the residual layer over ``blob`` would cost per image at ``max_error`` (an int -> float64 [n]; a list of ints ->
+        [n, len]), without coding anything: the exact coded cost of the tables ``add_residual`` would choose + 32 bits per
+        flushed lane state (entropy_coding.Codec.residual_bits)."""
+        self._check_residual_arguments("residual_bits", max_error)
+        return self._get_codec().residual_bits(x, blob, max_error)
 
     def rd_curve(self, x, steps=None, step_offsets=None):
         """The exact rate-distortion ladder of these images: what every ladder index of ``steps`` (None: the whole ladder,
