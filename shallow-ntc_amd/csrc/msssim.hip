@@ -5,6 +5,9 @@
 // sit in LDS and each thread evaluates the 11 x 11 Gaussian moments (mu_x, mu_y, E[xy], E[x^2 + y^2]) of
 // its pixel for every channel, then luminance and contrast-structure; per-(image, channel) sums are
 // reduced with wave shuffles + one double atomic per block.  The host finishes the (tiny) geometric mean.
+// The tile is centred while it is staged (one constant per tile and channel, subtracted from both images): covariance and
+// variances are shift-invariant, and E[x^2] - mu^2 of 0-255 data otherwise cancels in float32 (msssim_grad.hip
+// does the same); the luminance term uses the true means.
 #include <cmath>
 #include "sntc_internal.h"
 
@@ -29,13 +32,20 @@ __global__ void __launch_bounds__(256) ssim_scale_kernel(const float* __restrict
   const int ho = h - kWin + 1, wo = w - kWin + 1;
   const float* ab = a + (size_t)img * h * w * C;
   const float* bb = b + (size_t)img * h * w * C;
+  float shift[C];
+  {
+    const int cy = min(oy0 + kIn / 2, h - 1), cx = min(ox0 + kIn / 2, w - 1);
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) shift[ch] = ab[((size_t)cy * w + cx) * C + ch];
+  }
   for (int i = threadIdx.x; i < kIn * kIn * C; i += 256) {
     const int ch = i % C;
     const int p = i / C;
     const int ly = p / kIn, lx = p - ly * kIn;
     const int iy = min(oy0 + ly, h - 1), ix = min(ox0 + lx, w - 1);     // clamped reads feed masked outputs only
-    sa[i] = ab[((size_t)iy * w + ix) * C + ch];
-    sb[i] = bb[((size_t)iy * w + ix) * C + ch];
+    const float s = ch == 0 ? shift[0] : (ch == 1 ? shift[1 % C] : shift[2 % C]);    // selects, not a register array index
+    sa[i] = ab[((size_t)iy * w + ix) * C + ch] - s;
+    sb[i] = bb[((size_t)iy * w + ix) * C + ch] - s;
   }
   __syncthreads();
   const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
@@ -61,9 +71,9 @@ __global__ void __launch_bounds__(256) ssim_scale_kernel(const float* __restrict
       exy += wi * rxy;
       esq += wi * rsq;
     }
-    const float num0 = 2.0f * m0 * m1, den0 = m0 * m0 + m1 * m1;
-    const float lum = (num0 + c1) / (den0 + c1);
-    const float cs = (2.0f * exy - num0 + c2) / (esq - den0 + c2);
+    const float cs = (2.0f * exy - 2.0f * m0 * m1 + c2) / (esq - (m0 * m0 + m1 * m1) + c2);     // centred moments
+    const float ta = m0 + shift[ch], tb = m1 + shift[ch];                                       // the true means
+    const float lum = (2.0f * ta * tb + c1) / (ta * ta + tb * tb + c1);
     s_out[ch] = valid ? lum * cs : 0.0f;
     cs_out[ch] = valid ? cs : 0.0f;
   }
