@@ -1,6 +1,6 @@
 // rans_common.h -- what the rANS translation units share: the table views, the symbol of a value, the staging constants and
-// the host-side stream arithmetic.  rans.hip codes with a table id per element; rans_channels.hip with table = channel, from /
-// to floats; rans_cost.hip sums what the coded symbols cost.
+// the host-side stream arithmetic.  rans.hip codes with a table id per element and rans_channels.hip with table = channel, from /
+// to floats: both instantiate the one coder of rans_kernel.h; rans_cost.hip sums what the coded symbols cost.
 // The stream format is described once, at the head of rans.hip.
 #pragma once
 #include "sntc_internal.h"

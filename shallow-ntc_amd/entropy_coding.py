@@ -515,18 +515,23 @@ def _lanes(elems_per_stream, lanes=None):
     return 64 if elems_per_stream >= 16384 else 32 if elems_per_stream >= 6144 else 16 if elems_per_stream >= 2048 else 8
 
 
-def rans_encode_launch(values, table_ids, tables: DeviceTables, segments=None, lanes=None):
-    """The device half of ``rans_encode``: every stream coded into its own ``cap``-word scratch row, no host synchronisation.
-    -> (scratch int16 [streams, cap], lens int32 [streams]) for ``rans_encode_finish``."""
-    n = values.shape[0]
-    E = values.numel() // n
+def _encode_scratch(x, segments, lanes):
+    """What both encoder launches set up for the tensor ``x`` [n, ...] they code: the stream geometry and a ``cap``-word scratch
+    row + a length per stream.  -> (n, E, segments, lanes, cap, scratch int16 [streams, cap], lens int32 [streams])."""
+    n = x.shape[0]
+    E = x.numel() // n
     segments = _segments(E, segments)
     lanes = _lanes(-(-E // segments), lanes)
     cap = int(capi.load().sntc_rans_cap_words(E, segments))
-    dev = values.device
-    ns = n * segments
-    scratch = torch.empty((ns, cap), dtype=torch.int16, device=dev)
-    lens = torch.empty((ns,), dtype=torch.int32, device=dev)
+    scratch = torch.empty((n * segments, cap), dtype=torch.int16, device=x.device)
+    lens = torch.empty((n * segments,), dtype=torch.int32, device=x.device)
+    return n, E, segments, lanes, cap, scratch, lens
+
+
+def rans_encode_launch(values, table_ids, tables: DeviceTables, segments=None, lanes=None):
+    """The device half of ``rans_encode``: every stream coded into its own ``cap``-word scratch row, no host synchronisation.
+    -> (scratch int16 [streams, cap], lens int32 [streams]) for ``rans_encode_finish``."""
+    n, E, segments, lanes, cap, scratch, lens = _encode_scratch(values, segments, lanes)
     capi.call("sntc_rans_encode", _p(values), _p(table_ids), n, E, segments, lanes, _p(tables.cdf), _p(tables.meta), tables.ntables,
               tables.total, cap, _p(scratch), _p(lens), ops._stream())
     return scratch, lens
@@ -550,10 +555,10 @@ def rans_encode(values, table_ids, tables: DeviceTables, segments=None, lanes=No
     return rans_encode_finish(scratch, lens, lens_h), lens_h
 
 
-def rans_decode(payload, lens_h, table_ids, shape, tables: DeviceTables, segments=None, lanes=None, bad=None, offsets=None):
-    """-> int32 values of ``shape`` [n, ...]; raises on a malformed stream.  ``bad`` (an int32 device tensor [1]): count the
-    streams that did not terminate cleanly there instead of reading the count back here -- the caller checks it where it
-    synchronises anyway (a decoder that keeps several batches in flight)."""
+def _decode_setup(shape, out_dtype, payload, lens_h, tables, segments, lanes, bad, offsets):
+    """What both decoders set up before their launch: the stream geometry of ``shape`` [n, ...], the offsets on the device, the
+    output tensor, the counter of malformed streams (``bad``, or a fresh one) and the decoder's own tables where they are used.
+    -> (n, E, segments, lanes, offsets, out, bad, (dec, lut, lut_meta, lut_total) as call arguments)."""
     n = shape[0]
     E = int(np.prod(shape)) // n
     segments = _segments(E, segments)
@@ -563,18 +568,31 @@ def rans_decode(payload, lens_h, table_ids, shape, tables: DeviceTables, segment
     dev = payload.device
     if offsets is None:        # ``offsets``: the exclusive prefix sum of lens_h already on the device (int64 [streams + 1])
         offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(lens_h)]).astype(np.int64)).to(dev)
-    values = torch.empty(tuple(shape), dtype=torch.int32, device=dev)
-    deferred = bad is not None
-    if not deferred:
+    out = torch.empty(tuple(shape), dtype=out_dtype, device=dev)
+    if bad is None:
         bad = torch.zeros((1,), dtype=torch.int32, device=dev)
     fast = USE_START_TABLES and tables.dec is not None
+    dec = (_p(tables.dec if fast else None), _p(tables.lut if fast else None), _p(tables.lut_meta if fast else None),
+           tables.lut_total if fast else 0)
+    return n, E, segments, lanes, offsets, out, bad, dec
+
+
+def _raise_if_bad(bad, streams):
+    nbad = int(bad.item())
+    if nbad:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {streams} rANS streams did not terminate cleanly")
+
+
+def rans_decode(payload, lens_h, table_ids, shape, tables: DeviceTables, segments=None, lanes=None, bad=None, offsets=None):
+    """-> int32 values of ``shape`` [n, ...]; raises on a malformed stream.  ``bad`` (an int32 device tensor [1]): count the
+    streams that did not terminate cleanly there instead of reading the count back here -- the caller checks it where it
+    synchronises anyway (a decoder that keeps several batches in flight).  The decoder's start tables are used where
+    ``DeviceTables`` could place them (``tables.dec``); else the binary search of ``cdf``."""
+    n, E, segments, lanes, offsets, values, count, dec = _decode_setup(shape, torch.int32, payload, lens_h, tables, segments, lanes, bad, offsets)
     capi.call("sntc_rans_decode", _p(payload), _p(offsets), _p(table_ids), n, E, segments, lanes, _p(tables.cdf), _p(tables.meta),
-              tables.ntables, tables.total, _p(tables.dec if fast else None), _p(tables.lut if fast else None),
-              _p(tables.lut_meta if fast else None), tables.lut_total if fast else 0, _p(values), _p(bad), ops._stream())
-    if not deferred:
-        nbad = int(bad.item())
-        if nbad:
-            raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {n * segments} rANS streams did not terminate cleanly")
+              tables.ntables, tables.total, *dec, _p(values), _p(count), ops._stream())
+    if bad is None:
+        _raise_if_bad(count, n * segments)
     return values
 
 
@@ -602,14 +620,7 @@ def rans_encode_channels_launch(y, tables: DeviceTables, segments=None, lanes=No
     n, c = y.shape[0], y.shape[-1]
     if c != tables.ntables:
         raise capi.SntcError(capi.ERR_BAD_SHAPE, f"rans_encode_channels: {c} channels, {tables.ntables} tables")
-    E = y.numel() // n
-    segments = _segments(E, segments)
-    lanes = _lanes(-(-E // segments), lanes)
-    cap = int(capi.load().sntc_rans_cap_words(E, segments))
-    dev = y.device
-    ns = n * segments
-    scratch = torch.empty((ns, cap), dtype=torch.int16, device=dev)
-    lens = torch.empty((ns,), dtype=torch.int32, device=dev)
+    n, E, segments, lanes, cap, scratch, lens = _encode_scratch(y, segments, lanes)
     y_hat = torch.empty_like(y) if want_y_hat else None
     capi.call("sntc_rans_encode_channels", _p(y), n, E, c, segments, lanes, _p(tables.cdf), _p(tables.meta), tables.total, cap,
               _p(scratch), _p(lens), _p(y_hat), ops._stream())
@@ -628,29 +639,14 @@ def rans_decode_channels(payload, lens_h, shape, tables: DeviceTables, segments=
     """``rans_decode`` for a latent whose table is its channel -> the values as float32 of ``shape`` [n, ..., C] (what the
     synthesis consumes).  ``bad`` / ``offsets`` as in ``rans_decode``.  The decoder's start tables are used where
     ``DeviceTables`` could place them (``tables.dec``); else the binary search of ``cdf``."""
-    n, c = shape[0], shape[-1]
+    c = shape[-1]
     if c != tables.ntables:
         raise capi.SntcError(capi.ERR_BAD_SHAPE, f"rans_decode_channels: {c} channels, {tables.ntables} tables")
-    E = int(np.prod(shape)) // n
-    segments = _segments(E, segments)
-    lanes = _lanes(-(-E // segments), lanes)
-    if len(lens_h) != n * segments:
-        raise capi.SntcError(capi.ERR_BAD_SHAPE, "stream count does not match the image / segment counts")
-    dev = payload.device
-    if offsets is None:
-        offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(lens_h)]).astype(np.int64)).to(dev)
-    y_hat = torch.empty(tuple(shape), dtype=torch.float32, device=dev)
-    deferred = bad is not None
-    if not deferred:
-        bad = torch.zeros((1,), dtype=torch.int32, device=dev)
-    fast = USE_START_TABLES and tables.dec is not None
+    n, E, segments, lanes, offsets, y_hat, count, dec = _decode_setup(shape, torch.float32, payload, lens_h, tables, segments, lanes, bad, offsets)
     capi.call("sntc_rans_decode_channels", _p(payload), _p(offsets), n, E, c, segments, lanes, _p(tables.cdf), _p(tables.meta),
-              tables.total, _p(tables.dec if fast else None), _p(tables.lut if fast else None),
-              _p(tables.lut_meta if fast else None), tables.lut_total if fast else 0, _p(y_hat), _p(bad), ops._stream())
-    if not deferred:
-        nbad = int(bad.item())
-        if nbad:
-            raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {n * segments} rANS streams did not terminate cleanly")
+              tables.total, *dec, _p(y_hat), _p(count), ops._stream())
+    if bad is None:
+        _raise_if_bad(count, n * segments)
     return y_hat
 
 

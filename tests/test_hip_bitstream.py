@@ -107,6 +107,49 @@ def test_start_tables_do_not_change_a_decoded_value(dev, monkeypatch):
         assert (start <= sym).all() and (cdf[start] <= (slots >> (16 - bits) << (16 - bits))).all()
 
 
+@pytest.mark.parametrize("E", [1024, 1040, 2048])
+def test_full_chunk_boundary_in_every_decoder(E, dev, monkeypatch):
+    """64 lanes, one stream, 16 tables = channels: 1024 elements are exactly one chunk in which every lane has an element in
+    every step (the decoders' all-lanes-active path) and no ragged step; 1040 add one step with 16 live lanes; 2048 are two
+    such chunks.  One escape in element 1023 and one in the last.  Words == rans_np.encode_stream from both encoders; the
+    id-tensor and the channel decoder, each with the start tables on and off, return the values and refuse a flipped word."""
+    from shallow_ntc_amd import _capi
+    from shallow_ntc_amd import entropy_coding as ec
+    C, lanes, first = 16, 64, 16
+    tabs = ec.normal_tables()[first:first + C]               # sigma 0.8 .. 5: narrow tables, a few bits per symbol
+    dt = ec.DeviceTables(tabs, dev)
+    assert dt.dec is not None
+    rng = np.random.default_rng(E)
+    tid = (np.arange(E) % C).astype(np.int16)
+    sig = np.array([0.11 * np.exp(ec.SCALE_FACTOR * (first + k)) for k in range(C)])
+    vals = np.rint(rng.laplace(0, 1, size=E) * sig[tid] * 1.5).astype(np.int32)
+    vals[1023], vals[E - 1] = -20000, 20000
+    shape = (1, E // C, C)
+    vd, td = torch.from_numpy(vals).to(dev).view(shape), torch.from_numpy(tid).to(dev).view(shape)
+    payload, lens = ec.rans_encode(vd, td, dt, 1, lanes)
+    assert payload.cpu().numpy().view(np.uint16).tolist() == rans_np.encode_stream(vals, tid, tabs, lanes)
+    ch_payload, ch_lens, _ = ec.rans_encode_channels(vd.float(), dt, 1, lanes)
+    assert ch_lens.tolist() == lens.tolist() and torch.equal(ch_payload, payload)
+    assert len(payload) > 2 * lanes + 16                     # the flipped word below is a stream word, not a lane state
+    bad = payload.clone()
+    bad[2 * lanes + (len(payload) - 2 * lanes) // 2] ^= 0x0440
+    decoders = (lambda p: ec.rans_decode(p, lens, td, shape, dt, 1, lanes).cpu().numpy(),
+                lambda p: ec.rans_decode_channels(p, lens, shape, dt, 1, lanes).cpu().numpy())
+    for use in (True, False):
+        monkeypatch.setattr(ec, "USE_START_TABLES", use)
+        for decode in decoders:
+            np.testing.assert_array_equal(decode(payload).ravel(), vals, err_msg=f"start tables {use}")
+            with pytest.raises(_capi.SntcError, match="corrupt"):
+                decode(bad)
+    # a segment larger than any encoder writes (cap_words > 0x3fffffff) is refused at the entry point, before any launch
+    import ctypes as C_
+    P = lambda t: C_.c_void_p(t.data_ptr())
+    offs, out, badc = torch.zeros((2,), dtype=torch.int64, device=dev), torch.empty(shape, dtype=torch.int32, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)
+    with pytest.raises(_capi.SntcError):
+        _capi.call("sntc_rans_decode", P(payload), P(offs), P(td), 1, 1 << 30, 1, lanes, P(dt.cdf), P(dt.meta), dt.ntables, dt.total, None, None,
+                   None, 0, P(out), P(badc), None)
+
+
 def test_codec_round_trip_and_rate(dev):
     """compress -> bytes -> decompress == decode(encode(x)) bit for bit; the coded size is within a few percent
     of the estimated rate (integer scale table + 16-bit frequencies + escapes + per-stream headers)."""
@@ -250,7 +293,7 @@ def test_many_blobs_of_mixed_sizes_in_any_order(dev):
     assert ops.stream_k_enabled() == was                   # the static-schedule blocks left the process-wide switch as they found it
 
 
-# csrc/rans.hip kRansLdsLimit: a table set larger than this (table_bytes = 8 per table + 2 per cdf entry) is read from global memory
+# csrc/rans_kernel.h, kRansLdsTotal - kStagingBytes: a table set larger than this (table_bytes = 8 per table + 2 per cdf entry) is read from global memory
 # by rans_encode_kernel<false> / rans_decode_kernel<false> instead of being staged in LDS
 RANS_LDS_LIMIT = 150 * 1024 - (2 * 16 * 64 * 2 + 2 * 16 * 64 * 4)
 

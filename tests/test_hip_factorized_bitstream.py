@@ -99,6 +99,43 @@ def test_channel_coder_words_and_values(C, P, dev):
         np.testing.assert_array_equal(ec.rans_decode(payload, lens, tids_d, (n, P, C), dt, segs, lanes).cpu().numpy(), vals)
 
 
+@pytest.mark.parametrize("lanes", [8, 64])
+def test_an_empty_stream_in_both_coders(lanes, dev, monkeypatch):
+    """E = 260 (C = 5, P = 52) in 4 segments of 128 elements: the streams cover [0, 128), [128, 256), [256, 260) and nothing.
+    Per stream the words of both encoders == rans_np.encode_stream -- for the empty one the untouched lane states,
+    [1, 0] * lanes -- and both decoders return the values with the start tables on and off."""
+    from shallow_ntc_amd import entropy_coding as ec
+    C, P, n, segs = 5, 52, 2, 4
+    E = C * P
+    tabs = ec.factorized_tables(noisy_prior(C), 4)
+    dt = ec.DeviceTables(tabs, dev)
+    assert dt.dec is not None and ec._segments(E, segs) == segs
+    slices = stream_slices(E, segs)
+    assert [(sl.start, sl.stop) for sl in slices] == [(0, 128), (128, 256), (256, 260), (384, 260)]
+    y, vals = latents(np.random.default_rng(lanes), tabs, n, P)
+    yd = torch.from_numpy(y).to(dev)
+    vi = ec.round_to_int(yd)
+    tids_d = ec.channel_table_ids((n, P, 1, C), dev).view(n, P, C)
+    tid = np.arange(E) % C
+    payload, lens, _ = ec.rans_encode_channels(yd, dt, segs, lanes)
+    id_payload, id_lens = ec.rans_encode(vi, tids_d, dt, segs, lanes)
+    assert lens.tolist() == id_lens.tolist() and torch.equal(payload, id_payload)
+    words = payload.cpu().numpy().view(np.uint16)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    assert len(lens) == n * segs
+    for b in range(n):
+        for g, sl in enumerate(slices):
+            s = b * segs + g
+            ref = rans_np.encode_stream(vals[b].ravel()[sl], tid[sl], tabs, lanes)
+            assert words[off[s]:off[s + 1]].tolist() == ref, (b, g)
+        assert words[off[b * segs + 3]:off[b * segs + 4]].tolist() == [1, 0] * lanes
+    for use in (True, False):
+        monkeypatch.setattr(ec, "USE_START_TABLES", use)
+        back = ec.rans_decode_channels(payload, lens, (n, P, C), dt, segs, lanes)
+        np.testing.assert_array_equal(back.cpu().numpy(), np.clip(vals, -32768, 32767).astype(np.float32), err_msg=f"start tables {use}")
+        np.testing.assert_array_equal(ec.rans_decode(payload, lens, tids_d, (n, P, C), dt, segs, lanes).cpu().numpy(), vals)
+
+
 def wide_tables(C, symbols):
     """C tables of ``symbols`` real symbols each (a discretised Laplace of a width that depends on the channel) + ESCAPE."""
     from shallow_ntc_amd import entropy_coding as ec

@@ -102,11 +102,22 @@ LEDGER.update({
     "wgrad<default>": "test_hip_train.py::test_conv_wgrad_gather_side_every_tile_width",
     "colsum<true>": "test_hip_train.py::test_conv_wgrad_and_bias_grad",
     "colsum<false>": "test_hip_train.py::test_conv_wgrad_gather_side_every_tile_width",
+    # the ten instances of the rANS coder (csrc/rans_kernel.h): element source x direction x table placement / symbol search
     "rans_encode<true>": "test_hip_bitstream.py::test_stream_words_match_python_restatement, "
                          "test_hip_bitstream.py::test_table_set_beyond_the_lds_limit",
     "rans_encode<false>": "test_hip_bitstream.py::test_table_set_beyond_the_lds_limit",
-    "rans_decode<true>": "test_hip_bitstream.py::test_table_set_beyond_the_lds_limit",
+    "rans_decode<true>": "test_hip_bitstream.py::test_table_set_beyond_the_lds_limit, "
+                         "test_hip_bitstream.py::test_full_chunk_boundary_in_every_decoder",
     "rans_decode<false>": "test_hip_bitstream.py::test_table_set_beyond_the_lds_limit",
+    "rans_decode_fast": "test_hip_bitstream.py::test_start_tables_do_not_change_a_decoded_value, "
+                        "test_hip_bitstream.py::test_full_chunk_boundary_in_every_decoder",
+    "rans_encode_channels<true>": "test_hip_factorized_bitstream.py::test_channel_coder_words_and_values",
+    "rans_encode_channels<false>": "test_hip_factorized_bitstream.py::test_every_table_placement_decodes_the_same_values",
+    "rans_decode_channels<true>": "test_hip_factorized_bitstream.py::test_every_table_placement_decodes_the_same_values, "
+                                  "test_hip_factorized_bitstream.py::test_an_empty_stream_in_both_coders",
+    "rans_decode_channels<false>": "test_hip_factorized_bitstream.py::test_every_table_placement_decodes_the_same_values",
+    "rans_decode_channels_fast": "test_hip_factorized_bitstream.py::test_channel_coder_words_and_values, "
+                                 "test_hip_factorized_bitstream.py::test_every_table_placement_decodes_the_same_values",
 })
 
 
@@ -154,6 +165,23 @@ def _switch_cases(fname, anchor, label):
     return out
 
 
+def _rans_instances():
+    """The rANS coder's kernels in csrc/rans.hip and csrc/rans_channels.hip, as launched: rans_launch(k<true>, k<false>, ...) is
+    the table-placement dispatch (tables staged in LDS or read from global memory), the start-table decoders are launched
+    directly.  Every coder kernel the two files define must be launched, in every instance: a `template <bool LDS>` one in both."""
+    launched, defined = set(), set()
+    for fname in ("rans.hip", "rans_channels.hip"):
+        text = (CSRC / fname).read_text()
+        for k in re.findall(r"rans_launch\(\s*(rans_\w+?)_kernel\s*<\s*true\s*>\s*,\s*\1_kernel\s*<\s*false\s*>", text):
+            launched |= {f"{k}<true>", f"{k}<false>"}
+        launched |= set(re.findall(r"hipLaunchKernelGGL\(\s*(rans_(?:en|de)code\w*?)_kernel\s*,", text))
+        for tmpl, k in re.findall(r"(template\s*<\s*bool\s+LDS\s*>\s*)?__global__\s+void\s+(?:__launch_bounds__\(\d+\)\s+)?"
+                                  r"(rans_(?:en|de)code\w*?)_kernel\s*\(", text):
+            defined |= {f"{k}<true>", f"{k}<false>"} if tmpl else {k}
+    assert launched == defined and len(defined) == 10, (sorted(launched ^ defined), len(defined))
+    return launched
+
+
 def compiled_instances():
     out = _compiled_gg_instances()
     out |= _switch_cases("pixel.hip", "launch_gdn<4>", "gdn_small")
@@ -162,9 +190,7 @@ def compiled_instances():
     out |= _switch_cases("rgb_conv.hip", "RGB_LAUNCH(4)", "rgb_conv")
     out |= _switch_cases("wgrad.hip", "SNTC_WG_LAUNCH(1, 1)", "wgrad")
     out |= {f"colsum<{v}>" for v in re.findall(r"colsum_kernel\s*<\s*(true|false)\s*>", (CSRC / "wgrad.hip").read_text())}
-    # the table-set size dispatch of sntc_rans_encode / sntc_rans_decode (tables staged in LDS or read from global memory)
-    out |= {f"rans_{k}<{v}>" for k, v in re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*rans_(encode|decode)_kernel\s*<\s*(true|false)\s*>",
-                                                   (CSRC / "rans.hip").read_text())}
+    out |= _rans_instances()
     return out
 
 
