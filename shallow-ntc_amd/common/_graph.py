@@ -215,7 +215,7 @@ class ResidualBlock:
         c = cin
         for l in self._convs:
             c = l.build(w, c)
-        # the whole block as one launch (csrc/rb_fused.hip), bit-identical to the three layers below
+        # the whole block as one launch (csrc/rb_kernel.h; fp32 policy: csrc/rb_fused.hip), bit-identical to the three layers below
         self._block = None
         if (ops.FUSE_RESIDUAL_BLOCK or self.precision != "fp32") and ops.ResBlockPlan.supported(cin):
             n = self.name
@@ -228,7 +228,7 @@ class ResidualBlock:
         a, b, c = self._convs
         if self.precision != "fp32":
             # split-precision model: which arithmetic a layer takes may depend on the layer and on ONE image's geometry, never on
-            # the batch (DualPlan).  c = 192: ALWAYS the split-precision block (csrc/rb_fused_bf3.hip), whatever the launch size;
+            # the batch (DualPlan).  c = 192: ALWAYS the split-precision block (csrc/rb_kernel.h on csrc/rb_fused_bf3.hip), whatever the launch size;
             # other widths: the three fp32 layers (bit-identical for any batch)
             if self._block is not None and x.dtype == torch.float32:
                 return self._block(x)

@@ -1,5 +1,6 @@
-// rb_common.h -- what the two instantiations of the whole-ResidualBlock kernel share (rb_fused.hip: exact fp32;
-// rb_fused_bf3.hip: bf16 x 3 split precision): tile geometry, kernel arguments, small device helpers.
+// rb_common.h -- what the whole-ResidualBlock kernel's body (rb_kernel.h), its two arithmetic policies and their host code
+// (rb_fused.hip: exact fp32; rb_fused_bf3.hip: bf16 x 3 split precision) share: tile geometry, kernel arguments, small
+// device helpers.
 #pragma once
 #include <type_traits>
 #include "sntc_internal.h"
@@ -96,9 +97,10 @@ __device__ __forceinline__ void quad_transpose(f32x4 (&T)[4], int lane_in_quad) 
 
 }  // namespace rb
 
-// bf16 x 3 instantiation (rb_fused_bf3.hip)
-int rb3_init();
-size_t rb3_pack_bytes();                                    // bytes of the packed split-precision weight stream (c = 192)
+// bf16 x 3 instantiation (rb_fused_bf3.hip): what the host code of rb_fused.hip needs of it
+const void* rb3_kernel_ptr();                               // for the per-device once-init (its dynamic LDS limit)
+size_t rb3_lds_bytes();
+size_t rb3_pack_bytes();                                  // bytes of the packed split-precision weight stream (c = 192)
 int rb3_pack(const float* w0, const float* w1, const float* w2, void* wpack3, hipStream_t s);
 int rb3_launch(const rb::RBArgs& a, int grid, hipStream_t s);
 

@@ -24,7 +24,7 @@ FUSE_RESIDUAL_TAIL = True   # ResidualBlock (c = 192): 3x3 and 1x1 + skip in one
 MEAN_ONLY_HYPER = True      # decode: the hyper-synthesis' last layer computes its mu channels only (ConvPlan.columns; the same bits as the
                             # first half of the whole layer; False: the whole layer, for the A/B and the bit-identity tests)
 FUSE_RESIDUAL_BLOCK = not os.environ.get("SNTC_NO_RB_FUSE")   # ResidualBlock (c = 192): head, 3x3 and tail + skip in ONE launch on an 8 x 32
-                            # pixel tile with its halo patch in LDS (csrc/rb_fused.hip; bit-identical to the three launches)
+                            # pixel tile with its halo patch in LDS (csrc/rb_kernel.h on the fp32 policy of csrc/rb_fused.hip; bit-identical to the three launches)
 FUSED_BLOCK_MIN_TILES = 256  # ... where the launch offers at least one 8 x 32 tile per CU (one workgroup per CU); below, the layers
 CONCURRENT_BRANCHES = not os.environ.get("SNTC_NO_BRANCH_STREAMS")   # SimpleAttention: trunk and branch on two streams when the launches are small
 CONCURRENT_BRANCH_MAX_TILES = 1024  # ... i.e. up to a few 8 x 32 pixel tiles per CU (two launches then share the rounds a single one leaves ragged)
@@ -157,7 +157,8 @@ class PlanGroup:
 
 
 class ResBlockPlan:
-    """One whole ResidualBlock (reference common/elic.py:41-68) as one launch: sntc_resblock_plan (csrc/rb_fused.hip).
+    """One whole ResidualBlock (reference common/elic.py:41-68) as one launch: sntc_resblock_plan (host code and fp32
+    arithmetic in csrc/rb_fused.hip, the kernel's tile walk in csrc/rb_kernel.h).
     ``w0`` [1,1,c,c/2], ``w1`` [3,3,c/2,c/2], ``w2`` [1,1,c/2,c] are the Keras kernels, ``b*`` the biases or None."""
 
     @staticmethod
@@ -165,7 +166,7 @@ class ResBlockPlan:
         return bool(capi.load().sntc_resblock_supported(int(c)))
 
     def __init__(self, w0, b0, w1, b1, w2, b2, precision="fp32"):
-        """``precision`` "bf16x3": the split-precision instantiation (csrc/rb_fused_bf3.hip) -- fp32-level accuracy, not
+        """``precision`` "bf16x3": the same tile walk on the split-precision policy (csrc/rb_fused_bf3.hip) -- fp32-level accuracy, not
         bit-identical to "fp32"; fp32 tensors in and out either way."""
         capi.require_gpu()
         if precision not in ("fp32", "bf16x3"):

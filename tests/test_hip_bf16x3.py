@@ -2,6 +2,10 @@
 (-m gpu): the S3 format, the 256-wide direct-to-LDS kernel over the layer shapes of the decoders (phase-grouped transposed
 convolutions, forward convolutions, epilogues), schedule / tile / batch invariance, and the model-level bars of BASELINE.json
 (|d bpp| <= 1e-4, |d PSNR| <= 1e-3 dB against the oracle; compress -> decompress round trip in the same arithmetic)."""
+import hashlib
+import json
+from pathlib import Path
+
 import numpy as np
 import pytest
 import torch
@@ -10,6 +14,8 @@ from oracle import model_np
 from oracle import ops_np as O
 
 pytestmark = pytest.mark.gpu
+
+RESBLOCK_DIGESTS = json.loads((Path(__file__).resolve().parent / "golden" / "resblock_bf16x3.json").read_text())["sha256"]
 
 
 def dev_t(a, dev):
@@ -251,11 +257,12 @@ def test_split_precision_analysis_does_not_depend_on_the_batch(dev):
     assert torch.equal(p4[2:3], p1)
 
 
-@pytest.mark.parametrize("n,h,w", [(1, 8, 32), (2, 13, 45), (1, 64, 96), (3, 37, 100), (2, 40, 33)])
+@pytest.mark.parametrize("n,h,w", [(1, 8, 32), (2, 13, 45), (1, 5, 7), (1, 64, 96), (3, 37, 100), (2, 40, 33)])
 def test_whole_residual_block_in_split_precision(n, h, w, dev):
     """sntc_resblock_forward with precision 1 (csrc/rb_fused_bf3.hip; reference common/elic.py:41-68): the whole c = 192 block in
     bf16 x 3 on pre-split weights, pixels split in registers -- fp32-level accuracy against the float64 oracle (within 4x the exact
-    fp32 block's own error), the same bits for any number of persistent workgroups and for an image alone or inside a batch."""
+    fp32 block's own error), the same bits for any number of persistent workgroups (8: the XCD remap of the tile range) and for an
+    image alone or inside a batch; on the shapes of tests/golden/resblock_bf16x3.json the output bytes are the recorded ones."""
     from shallow_ntc_amd import ops
     rng = np.random.default_rng(77 * n + h + w)
     c = 192
@@ -275,7 +282,12 @@ def test_whole_residual_block_in_split_precision(n, h, w, dev):
     y = split(xd)
     e3 = rel_err(y.cpu().numpy(), ref)
     assert e3 < 5e-6 and e3 < 4 * e32 + 2e-7, (e3, e32)
-    for wg in (1, 3, 200):
+    want = RESBLOCK_DIGESTS.get(f"{n},{h},{w}")
+    if want is not None:
+        got = hashlib.sha256(y.cpu().numpy().tobytes()).hexdigest()
+        assert got == want, (f"bf16 x 3 ResidualBlock output of {n}x{h}x{w} has SHA-256 {got}, recorded {want}: re-record "
+                             "tests/golden/resblock_bf16x3.json only with a deliberate change of the split arithmetic")
+    for wg in (1, 3, 8, 200):
         split.set_workgroups(wg)
         assert torch.equal(split(xd), y), wg
     split.set_workgroups(0)

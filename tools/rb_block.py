@@ -1,4 +1,4 @@
-"""Time the whole-ResidualBlock launch (csrc/rb_fused.hip) against the layers it replaces (1x1 head + fused 3x3 / 1x1 tail),
+"""Time the whole-ResidualBlock launch (csrc/rb_kernel.h: fp32 in csrc/rb_fused.hip, bf16 x 3 in csrc/rb_fused_bf3.hip) against the layers it replaces (1x1 head + fused 3x3 / 1x1 tail),
 bursts of launches between HIP events, interleaved rounds in one process.  python tools/rb_block.py [n h w]..."""
 import sys
 from pathlib import Path

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Cycles per phase of the two ResidualBlock kernels -- needs a DIAG build (make -C shallow-ntc_amd/csrc clean && make DIAG=1):
-the kernel then overwrites the first floats of its output with s_memtime sums per workgroup (csrc/rb_fused_bf3.hip)."""
+the kernel then overwrites the first floats of its output with s_memtime sums per workgroup (RB_STAMP in csrc/rb_kernel.h, the body both kernels
+instantiate)."""
 import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
