@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <vector>
 #include "sntc_internal.h"
+#include "gg_tap_rules.h"
 
 namespace sntc {
 
@@ -288,6 +289,9 @@ static int build_plan(sntc_conv_plan* p, const float* weight, const float* bias,
     for (int t = 0; t < G.T; ++t) G.tw = std::max(G.tw, (hg.taps[t] & 0xffff) + 1);
     for (int t = 0; t < G.T; ++t)     // the kernel walks taps arithmetically: (t / tw, t % tw)
       if (hg.taps[t] != (((t / G.tw) << 16) | (t % G.tw))) return fail(SNTC_ERR_UNSUPPORTED, "tap table is not a dense row-major grid");
+    // the vector loader keeps one in-range bit per tap row and tap column of a tile row (gg_tap_rules.h)
+    if (p->vec && (G.tw > kTapGridMax || G.T / G.tw > kTapGridMax))
+      return fail(SNTC_ERR_UNSUPPORTED, "tap grid of a phase group is wider or taller than 16 taps: beyond the vector loader's tap masks");
     G.K = p->rowpack ? G.T * kStage : ((G.T * d.cin + kStage - 1) / kStage) * kStage;
     if ((int64_t)G.Ncol * G.K * 4 >= (1LL << 31)) return fail(SNTC_ERR_UNSUPPORTED, "packed weights of one phase group must be < 2 GiB");
     SNTC_HIP(hipMalloc(&G.taps, sizeof(int) * std::max(1, G.T)));

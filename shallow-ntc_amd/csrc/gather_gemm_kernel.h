@@ -11,7 +11,10 @@
 //   HBM/L2 -> registers: buffer_load_dwordx4 through two wave-uniform descriptors (input, packed weights) with a
 //   32-bit per-lane byte offset that changes only when the tap changes and a scalar offset that walks the channel
 //   slabs / K stages; rows whose source pixel falls outside the image carry an out-of-range offset and read zeros
-//   from the bounds check (no branches, no 64-bit address arithmetic in the loop).  Cin % 16 != 0 (the RGB first
+//   from the bounds check (no branches, no 64-bit address arithmetic in the loop).  The per-lane offset of a tap is
+//   base + delta with bit 31 set unless (mask & select) == select (gg_tap_rules.h): base (tap (0, 0) of the row) and mask
+//   (which tap rows / columns of the row are inside the image) are made once per tile, delta and select are scalars the
+//   tap walk advances with adds -- 4 vector instructions per row and stage, no multiply.  Cin % 16 != 0 (the RGB first
 //   layer, reduced-width test nets) takes the dword gather path: one k column per thread, (tap, channel) advanced
 //   incrementally, same bounds-check zero fill.
 //   registers -> LDS: a ring of THREE 16-deep stages, 64-B rows, 16-B chunks XOR-swizzled by (row >> 2) & 3, so the
@@ -36,6 +39,7 @@
 #include <mutex>
 #include <type_traits>
 #include "sntc_internal.h"
+#include "gg_tap_rules.h"
 
 namespace sntc {
 
@@ -181,7 +185,15 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
   constexpr int EPW = 32 * (TN >= 2 ? 64 : 32);       // floats of epilogue staging per wave
   constexpr bool DBUF = !BF3 && TM * TN <= 8 && TN <= 5;   // fragment double buffering (the two widest 32-row tiles, 96+ accumulator
                                                       // registers and 7-8 fragment quads, run single-buffered)
-  constexpr bool RBUF = DBUF && TM * TN <= 3 && !FUSE2;         // second staging register set for a tile's first two stages
+  // TWO: two staging register sets alternate through the whole K loop (stage s lives in set s & 1): the global loads of stage
+  // j+4 are issued in step j into the set step j has just written to LDS, two steps before step j+2 writes them -- twice the
+  // lead of the single set, for no LDS.  OFF in the shipped library (kGGTwoSets, sntc_internal.h): it measured 4 - 6 % SLOWER
+  // on the hyper-synthesis launches, with the same bits.  Compiled only where the second set fits the instance's
+  // waves per SIMD without a spill: the one- and two-tile instances (128 x 64: 167 of 168 registers) and the 2 x 2-tile
+  // 128 x 128 one with its column-major twin; 128 x 96 sits at 163 of 168 registers, the 1 x 4-tile 128 x 128 instance spills
+  // 71 registers with a second set and the wider tiles have no room: they keep the single set either way
+  constexpr bool TWO = kGGTwoSets && VEC && DBUF && !DMA && !FUSE2 && (TM * TN <= 2 || (TM == 2 && TN == 2));
+  constexpr bool RBUF = TWO || (DBUF && TM * TN <= 3 && !FUSE2);   // second staging register set for a tile's first two stages
   static_assert(RING * SLOT >= 4 * EPW + (DMA ? SLOT : 0), "epilogue staging (and one prefetched stage) must fit in the stage ring");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* ring = reinterpret_cast<float*>(smem);                  // [RING][BM + BN][16]
@@ -359,6 +371,11 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
   int a_iy0[NROW], a_ix0[NROW];
   unsigned a_img[NROW];           // byte offset of the row's image (+ chunk), or kOutOfRange for padding rows
   unsigned a_off[NROW];           // vector path: current tap's byte offset per row
+  // vector path (kGGTapState): per-tile row state of gg_tap_rules.h -- byte offset of tap (0, 0) mod 2^32, and the taps whose
+  // image row (bits 0..15) / column (bits 16..31) is inside the image -- so that a tap change costs an add and a mask test
+  unsigned a_base[NROW], a_mask[NROW];
+  unsigned ld_delta = 0, ld_sel = 0x10001u;     // wave-uniform: the current tap's byte delta against tap (0, 0), its select word
+  unsigned tap_dx = 0, tap_drow = 0;            // delta steps: next tap in the row; first tap of the next row
   unsigned b_off[B_CH];
   int ld_stage = 0, ld_t = 0, ld_cc = 0;        // next stage to load; vector path: its (tap, channel slab)
   int ld_ty = 0, ld_tx = 0;                     // vector path: the tap's (row, column) in the group's tw-wide tap grid
@@ -370,6 +387,11 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
   int m0 = 0, n0 = 0;
 
   auto set_tap = [&](int ty, int tx) {
+    if constexpr (kGGTapState) {
+#pragma unroll
+      for (int i = 0; i < NROW; ++i) a_off[i] = gg_tap_offset(a_base[i], a_mask[i], ld_delta, ld_sel);
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < NROW; ++i) {
       const int iy = a_iy0[i] + ty * a.tstep;
@@ -414,6 +436,11 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
 #pragma unroll
     for (int i = 0; i < NROW; ++i) {
       const int4 ri = rinfo[VEC ? r0 + 64 * i : rs + 16 * i];
+      if constexpr (VEC && kGGTapState) {
+        const TapGeo geo{a.H, a.W, a.Cin, a.sA, a.tstep, a.offy, a.offx};
+        gg_tap_row(geo, ri.x, ri.y, ri.z, ri.w, c, g_T / g_tw, g_tw, &a_base[i], &a_mask[i]);
+        continue;
+      }
       a_iy0[i] = ri.y * a.sA + a.offy;
       a_ix0[i] = ri.z * a.sA + a.offx;
       a_img[i] = ri.w ? (unsigned)ri.x * (unsigned)(a.H * a.W) * (unsigned)a.Cin * 4u + (VEC ? (unsigned)c * 16u : 0u)
@@ -436,6 +463,13 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
       ld_t = p.k0 - ld_cc * g_T;
       ld_ty = ld_t / g_tw;
       ld_tx = ld_t - ld_ty * g_tw;
+      if constexpr (kGGTapState) {
+        const TapGeo geo{a.H, a.W, a.Cin, a.sA, a.tstep, a.offy, a.offx};
+        tap_dx = gg_tap_dx(geo);
+        tap_drow = gg_tap_dy(geo) - (unsigned)(g_tw - 1) * tap_dx;
+        ld_delta = gg_tap_delta(geo, ld_ty, ld_tx);
+        ld_sel = gg_tap_select(ld_ty, ld_tx);
+      }
       set_tap(ld_ty, ld_tx);
     } else {
       const int k = p.k0 * kStage + kk;
@@ -456,8 +490,9 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
     ++ld_stage;
     if (VEC) {
       // next stage's channel slab / tap, without a branch (the steady-state loop stays one basic block: the scheduler
-      // can then place every load, LDS write and fragment read between MFMAs); the per-row offsets are recomputed every
-      // stage -- ~10 VALU per row against 1024 MFMA cycles
+      // can then place every load, LDS write and fragment read between MFMAs); the per-row offsets are re-made every
+      // stage from the row's (base, mask) and the scalar (delta, select) -- 4 VALU per row (kGGTapState off: the whole
+      // source-pixel formula, ~10 VALU per row with two quarter-rate multiplies)
       // K order of the vector path: channel slab OUTERMOST, taps inside (k = cc * T * 16 + t * 16 + c): the taps of one
       // 16-channel slab re-read the same input pixels (a 5x5 / stride-2 layer touches each ~6 times), so they now do it
       // within T consecutive stages, from L2, instead of T * Cin / 16 stages apart, from HBM
@@ -467,6 +502,10 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
       ld_ty = tap_end ? 0 : ld_ty + row_end;
       ld_t = tap_end ? 0 : ld_t + 1;
       ld_cc += tap_end;
+      if constexpr (kGGTapState) {          // scalar: the delta walks the tap grid with adds, and starts over at the slab's end
+        ld_delta = tap_end ? 0u : ld_delta + (row_end ? tap_drow : tap_dx);
+        ld_sel = gg_tap_select(ld_ty, ld_tx);
+      }
       set_tap(ld_ty, ld_tx);
     }
   };
@@ -796,14 +835,17 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
       write_lds(R0, 1);
     }
     if (n > 2) load_regs(R0);
+    if (TWO && n > 3) load_regs(R1);           // two sets: stages k0+2 and k0+3 in flight
     __syncthreads();
     if (DBUF && n > 0) read_frag(F0, 0, 0);
 
     // one step = one stage.  WR: stage j+2 goes from registers into the ring; LD: stage j+3's global loads are issued;
     // PF: the first fragments of stage j+1 are prefetched.  The steady-state steps have all three and no branch.
-    auto step = [&](auto WR, auto LD, auto PF) {
-      if (decltype(WR)::value && !SNTC_DBG(a, 2)) write_lds(R0, s_n2);        // stage j+2, loaded during step j-1
-      if (decltype(LD)::value && !SNTC_DBG(a, 1)) load_regs(R0);              // stage j+3
+    // R: the staging set of the step (single set: always R0; TWO: the set of the step's parity, stage j+2 loaded during step
+    // j-2, stage j+4 issued now)
+    auto step = [&](Regs& R, auto WR, auto LD, auto PF) {
+      if (decltype(WR)::value && !SNTC_DBG(a, 2)) write_lds(R, s_n2);         // stage j+2, loaded during step j-1 (TWO: j-2)
+      if (decltype(LD)::value && !SNTC_DBG(a, 1)) load_regs(R);               // stage j+3 (TWO: j+4)
       if (BF3) {
         Frag3 F3;
         read_frag3(F3, s_cur);
@@ -842,10 +884,38 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
     };
     using Yes = std::integral_constant<bool, true>;
     using No = std::integral_constant<bool, false>;
-    for (int j = 0; j + 3 < n; ++j) step(Yes{}, Yes{}, Yes{});
-    if (n >= 3) step(Yes{}, No{}, Yes{});
-    if (n >= 2) step(No{}, No{}, Yes{});
-    if (n >= 1) step(No{}, No{}, No{});
+    if constexpr (TWO) {
+      // steady state: two steps per iteration, R0 on the even and R1 on the odd stages of the piece, no register copies.  ONE
+      // exit, after a whole pair (a second exit between the two steps made the compiler carry the accumulators out of the loop
+      // in a second register set: 16 to 32 v_mov_b64 per iteration); a fifth remaining step is the pair's first half again
+      int j = 0;
+      for (; j + 5 < n; j += 2) {
+        step(R0, Yes{}, Yes{}, Yes{});
+        step(R1, Yes{}, Yes{}, Yes{});
+      }
+      int rem = n - j;                         // 0 .. 5
+      bool odd = false;
+      if (rem == 5) {
+        step(R0, Yes{}, Yes{}, Yes{});
+        odd = true;
+        rem = 4;
+      }
+      // tail: up to two stages wait in the sets (stage j+2 in the set of j's parity, then stage j+3 in the other)
+      if (rem >= 4) {
+        if (odd) step(R1, Yes{}, No{}, Yes{}); else step(R0, Yes{}, No{}, Yes{});
+        odd = !odd;
+      }
+      if (rem >= 3) {
+        if (odd) step(R1, Yes{}, No{}, Yes{}); else step(R0, Yes{}, No{}, Yes{});
+      }
+      if (rem >= 2) step(R0, No{}, No{}, Yes{});
+      if (rem >= 1) step(R0, No{}, No{}, No{});
+    } else {
+      for (int j = 0; j + 3 < n; ++j) step(R0, Yes{}, Yes{}, Yes{});
+      if (n >= 3) step(R0, Yes{}, No{}, Yes{});
+      if (n >= 2) step(R0, No{}, No{}, Yes{});
+      if (n >= 1) step(R0, No{}, No{}, No{});
+    }
     }   // register-staged pipeline
 
     // ---- the next piece's first stages go in flight before this piece's results are stored

@@ -103,6 +103,21 @@ struct GGArgs {
 constexpr int kNumVariants = 10;   // fp32 variants
 constexpr int kMaxVariant = 13;
 constexpr int kStage = 16;         // K depth of one pipeline stage
+// Compile-time switches of the gather GEMM's vector loader (gather_gemm_kernel.h), for A/B builds of whole libraries
+// (make EXTRA=-DSNTC_GG_TAP_STATE=0 LIB=...; compare binaries through SNTC_LIB, never a run-time switch):
+//   kGGTapState  per-tap row offsets from per-tile (base, mask) and a scalar delta, instead of the per-stage multiply chain: ON
+//                (the 320-column HS3 launch 615 -> 594 us, the two-stream decode step 2.426 -> 2.392 ms, profiles/gg_loader_ab.json)
+//   kGGTwoSets   two staging register sets in the steady state: global loads issued two stages ahead of their LDS write: OFF --
+//                measured SLOWER than the single set (the same HS3 launch 615 -> 651 us alone, 594 -> 626 us on top of the tap
+//                state; the step 2.426 -> 2.570 / 2.521 ms), same bits; kept as a switch for the next look at the loads' lead
+#ifndef SNTC_GG_TAP_STATE
+#define SNTC_GG_TAP_STATE 1
+#endif
+#ifndef SNTC_GG_TWO_SETS
+#define SNTC_GG_TWO_SETS 0
+#endif
+constexpr bool kGGTapState = SNTC_GG_TAP_STATE != 0;
+constexpr bool kGGTwoSets = SNTC_GG_TWO_SETS != 0;
 
 // One compiled gather-GEMM instance (gather_gemm.hip holds the table).  schedule() in conv_plan.hip resolves a
 // launch to one row; residency, tile shape, slab size, LDS and the GGArgs mode fields all come from that row.
