@@ -28,28 +28,16 @@
 #include <algorithm>
 #include <type_traits>
 #include "sntc_internal.h"
+#include "gg_pieces.h"     // the piece walk and the stream-K hand-off, shared with gg_kernel
 
 namespace sntc {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
-constexpr unsigned kOOR = 0x80000000u;          // > any in-range offset: buffers are < 2 GiB (host check)
-constexpr int kSpin = 1 << 22;
-
-__device__ __forceinline__ float act_of(float v, int act) {
-  switch (act) {
-    case SNTC_ACT_RELU: return fmaxf(v, 0.0f);
-    case SNTC_ACT_LEAKY_RELU: return v >= 0.0f ? v : 0.2f * v;
-    case SNTC_ACT_SIGMOID: return 1.0f / (1.0f + expf(-v));
-    default: return v;
-  }
-}
-
+// the epilogues a pre-split plan can carry.  Not apply_epilogue: that one (with the GDN divisions and square roots no pre-split
+// layer has) lives in gather_gemm_kernel.h with the fp32 kernel template, which this translation unit does not include
 __device__ __forceinline__ f32x4 epi_of(f32x4 v, int epi, const f32x4 rs, const float* aux, size_t idx) {
   switch (epi) {
     case SNTC_EPI_ADD: return v + rs;
@@ -65,19 +53,6 @@ __device__ __forceinline__ f32x4 epi_of(f32x4 v, int epi, const f32x4 rs, const 
     default: return v;
   }
 }
-
-typedef const GGArgs __attribute__((address_space(4))) KArgs;
-__device__ __forceinline__ KArgs& kargs() {
-  KArgs* kp = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(kp));
-  return *kp;
-}
-
-struct Piece {
-  int gi, mt, nt, k0, k1;
-  int consume;   // worker whose published accumulators this piece continues (-1: start from zero)
-  int publish;   // 1: the tile is finished by the next worker
-};
 
 }  // namespace
 
@@ -109,123 +84,15 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) bf3_kernel(const GGArgs a) {
   const int wm = wave / WN, wn = wave % WN;
   const int l31 = lane & 31, h = lane >> 5;
 
-  // ---------------------------------------------------------------- the worker's pieces (stream-K: head, whole tiles, tail)
-  int sk_head_t = -1, sk_head_k1 = 0, sk_tail_t = -1, sk_tail_k0 = 0, sk_cur = 0, sk_last = -1, sk_phase = 0, wl = 0;
-  if (a.sk) {
-    const int w = blockIdx.x;
-    wl = (w & 7) * (a.nworkers >> 3) + (w >> 3);
-    const int u_lo = (int)(a.units * wl / a.nworkers), u_hi = (int)(a.units * (wl + 1) / a.nworkers);
-    // Unit order (a.order == 1, the default): row strip major, then group, then column tile -- every worker's share mixes the
-    // groups (their tiles differ in length: a group-major order hands some workers only short, epilogue-heavy tiles).
-    // a.order == 0: COLUMN tile outermost, row strips inside (u = ntm * unit0(g) + nt * ntm * steps + mt * steps + k): a tile's
-    // weight rows stay in one XCD's L2 while the strips stream past; measured equal on single-group layers and 20 % slower on
-    // the four-group synthesis, kept for the A/B.
-    auto locate = [&](int u, int* t, int* k, int* steps) {
-      int gi = 0;
-      if (a.order == 1) {
-        const int mt = u / a.ups;
-        const int r = u - mt * a.ups;
-#pragma unroll
-        for (int i = 1; i < kMaxGroups; ++i)
-          if (i < a.ngroups && r >= (int)a.g[i].unit0) gi = i;
-        const int r2 = r - (int)a.g[gi].unit0;
-        const int nt = r2 / a.g[gi].steps;
-        *t = mt * a.tps + a.g[gi].tile0 + nt;
-        *k = r2 - nt * a.g[gi].steps;
-      } else {
-#pragma unroll
-        for (int i = 1; i < kMaxGroups; ++i)
-          if (i < a.ngroups && u >= (int)a.g[i].unit0 * a.ntm) gi = i;
-        const int r = u - (int)a.g[gi].unit0 * a.ntm;
-        const int per = a.ntm * a.g[gi].steps;
-        const int nt = r / per;
-        const int r2 = r - nt * per;
-        const int mt = r2 / a.g[gi].steps;
-        *t = (a.g[gi].tile0 + nt) * a.ntm + mt;
-        *k = r2 - mt * a.g[gi].steps;
-      }
-      *steps = a.g[gi].steps;
-    };
-    if (u_hi > u_lo) {
-      int tF, kF, sF, tL, kL, sL;
-      locate(u_lo, &tF, &kF, &sF);
-      locate(u_hi - 1, &tL, &kL, &sL);
-      sk_cur = tF;
-      sk_last = tL;
-      if (kF > 0) { sk_tail_t = tF; sk_tail_k0 = kF; sk_cur = tF + 1; }
-      if (kL + 1 < sL) { sk_head_t = tL; sk_head_k1 = kL + 1; sk_last = tL - 1; }
-    } else {
-      sk_phase = 3;
-    }
-  }
-  auto tile_of = [&](int t, Piece* p) {
-    KArgs& a = kargs();
-    const int mt = a.order == 1 ? t / a.tps : t % a.ntm;
-    const int r = a.order == 1 ? t - mt * a.tps : t / a.ntm;
-    int gi = 0;
-#pragma unroll
-    for (int i = 1; i < kMaxGroups; ++i)
-      if (i < a.ngroups && r >= a.g[i].tile0) gi = i;
-    p->gi = gi; p->mt = mt; p->nt = r - a.g[gi].tile0;
-  };
-  // Order of a worker's pieces: head (published, depends on nothing), whole tiles, tail (continues the previous worker's
-  // chain: its head was computed first thing, so the tail never waits).  Whole-tiles-first was tried for lockstep L2 sharing:
-  // the tails then wait for heads of uneven length and the remainder phase doubles (HS2 172 -> 124 TFLOP/s-equivalent).
-  auto next_piece = [&](Piece* p) -> bool {
-    KArgs& a = kargs();
-    if (!a.sk) return false;
-    if (sk_phase == 0) {
-      sk_phase = 1;
-      if (sk_head_t >= 0) {
-        tile_of(sk_head_t, p);
-        p->k0 = 0; p->k1 = sk_head_k1; p->consume = -1; p->publish = 1;
-        return true;
-      }
-    }
-    if (sk_phase == 1) {
-      if (sk_cur <= sk_last) {
-        tile_of(sk_cur++, p);
-        p->k0 = 0; p->k1 = a.g[p->gi].steps; p->consume = -1; p->publish = 0;
-        return true;
-      }
-      sk_phase = 2;
-    }
-    if (sk_phase == 2) {
-      sk_phase = 3;
-      if (sk_tail_t >= 0) {
-        tile_of(sk_tail_t, p);
-        p->k0 = sk_tail_k0; p->k1 = a.g[p->gi].steps; p->consume = wl - 1; p->publish = 0;
-        return true;
-      }
-    }
-    return false;
-  };
-
+  // ---------------------------------------------------------------- the worker's pieces (gg_pieces.h)
+  PieceWalk<kOrderRuntime> walk;                   // stream-K: head, whole tiles, tail; unit order from GGArgs::order
   Piece P;
-  bool have;
   if (a.sk) {
-    have = next_piece(&P);
-  } else {                                         // static: one workgroup per tile, XCD-aware order (column tile fastest)
-    int gi = 0;
-#pragma unroll
-    for (int i = 1; i < kMaxGroups; ++i)
-      if (i < a.ngroups && (int)blockIdx.x >= a.g[i].blk0) gi = i;
-    const int lb = blockIdx.x - a.g[gi].blk0;
-    const int ntn = a.g[gi].ntn;
-    const int full = a.ntm & ~7;
-    if (lb < full * ntn) {
-      const int l = lb >> 3;
-      P.mt = (l / ntn) * 8 + (lb & 7);
-      P.nt = l % ntn;
-    } else {
-      const int r = lb - full * ntn, rem = a.ntm - full;
-      P.mt = full + r % rem;
-      P.nt = r / rem;
-    }
-    P.gi = gi; P.k0 = 0; P.k1 = a.g[gi].steps; P.consume = -1; P.publish = 0;
-    have = true;
+    walk.init(a, blockIdx.x);
+    if (!walk.next(fresh_args(), &P)) return;
+  } else {                                         // static: one workgroup per tile (ksplit == 1), XCD-aware order
+    static_piece(a, blockIdx.x, &P);
   }
-  if (!have) return;
 
   // ---------------------------------------------------------------- loader state
   const __amdgpu_buffer_rsrc_t xs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
@@ -274,29 +141,11 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) bf3_kernel(const GGArgs a) {
       const int ix = a_ix0[i] + tx * a.tstep;
       const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
       const unsigned pix = ((unsigned)(iy * a.W + ix) * (unsigned)a.Cin * 6u) & 0x7fffffffu;
-      a_off[i] = (a_img[i] + pix) | (ok ? 0u : kOOR);
-    }
-  };
-  auto write_rinfo = [&](const Piece& p, int rb) {
-    KArgs& a = kargs();
-    int4* rinfo = rinfo_all + rb * BM;
-    const int mbase = p.mt * BM;
-    const int q0y = a.g[p.gi].q0y, q0x = a.g[p.gi].q0x;
-    for (int r = tid; r < BM; r += NT) {
-      const int m = mbase + r;
-      int4 ri = make_int4(0, 0, 0, 0);
-      if (m < a.M) {
-        const int per = a.Qh * a.Qw;
-        const int n = m / per;
-        const int rem = m - n * per;
-        const int qy = rem / a.Qw;
-        ri = make_int4(n, qy + q0y, rem - qy * a.Qw + q0x, 1);
-      }
-      rinfo[r] = ri;
+      a_off[i] = (a_img[i] + pix) | (ok ? 0u : kOutOfRange);
     }
   };
   auto init_loader = [&](const Piece& p, int rb) {
-    KArgs& a = kargs();
+    KArgs& a = fresh_args();
     const int4* rinfo = rinfo_all + rb * BM;
     const auto& G = a.g[p.gi];
     g_T = G.T;
@@ -340,7 +189,7 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) bf3_kernel(const GGArgs a) {
           ok = y < H && x < W;
           pix = (unsigned)((n * H + y) * W + x);
         }
-        p_off[i] = ok ? pix * (unsigned)a.Cin * 6u + (unsigned)((part >> 1) * 32 + (((part & 1) ^ ((row >> 3) & 1)) << 4)) : kOOR;
+        p_off[i] = ok ? pix * (unsigned)a.Cin * 6u + (unsigned)((part >> 1) * 32 + (((part & 1) ^ ((row >> 3) & 1)) << 4)) : kOutOfRange;
       }
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
@@ -364,7 +213,7 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) bf3_kernel(const GGArgs a) {
         const int4 ri = rinfo[a_row[i]];
         a_iy0[i] = ri.y * a.sA + a.offy;
         a_ix0[i] = ri.z * a.sA + a.offx;
-        a_img[i] = ri.w ? (unsigned)ri.x * (unsigned)(a.H * a.W) * (unsigned)a.Cin * 6u + a_part[i] : kOOR;
+        a_img[i] = ri.w ? (unsigned)ri.x * (unsigned)(a.H * a.W) * (unsigned)a.Cin * 6u + a_part[i] : kOutOfRange;
       }
     }
 #pragma unroll
@@ -571,37 +420,13 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) bf3_kernel(const GGArgs a) {
 
   // ---------------------------------------------------------------- the piece loop
   int rb = 0;
-  write_rinfo(P, rb);
+  write_rinfo<BM, NT>(fresh_args(), P, rinfo_all + rb * BM, tid);
   __syncthreads();
   start_piece(P, rb);
   while (true) {
     const int n = __builtin_amdgcn_readfirstlane(P.k1 - P.k0);
     if (P.consume >= 0) {
-      if (tid == 0) {
-        int spins = 0;
-        while (__hip_atomic_load(a.sk_flags + P.consume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-          __builtin_amdgcn_s_sleep(8);
-          if (++spins > kSpin) {           // never hang, never trap: flag the launch (sntc_conv_status) and carry on
-            __hip_atomic_fetch_or(kargs().status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __syncthreads();
-      const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
-          a.sk_slab + (size_t)P.consume * (TM * TN * 16 * NT), 0, TM * TN * 16 * NT * 4, 0x00020000);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(sr, tid * 16, ((i * TN + j) * 4 + q) * NT * 16, 0);
-            const f32x4 f = __builtin_bit_cast(f32x4, v);
-            acc[i][j][4 * q] = f[0]; acc[i][j][4 * q + 1] = f[1]; acc[i][j][4 * q + 2] = f[2]; acc[i][j][4 * q + 3] = f[3];
-          }
+      sk_consume<TM, TN, NT>(a, P.consume, tid, acc);
     } else {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -808,38 +633,21 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) bf3_kernel(const GGArgs a) {
 
     // ---- the next piece's first two stages go in flight (ring slots 0 and 1) before this piece's results are stored
     Piece Q;
-    const bool more = next_piece(&Q);
+    const bool more = walk.next(fresh_args(), &Q);
     const int n0d = n0;
     const int4* rinfo = rinfo_all + rb * BM;
     __syncthreads();                  // every wave has read its last fragments: the whole ring is free
     if (more) {
-      write_rinfo(Q, rb ^ 1);
+      write_rinfo<BM, NT>(fresh_args(), Q, rinfo_all + (rb ^ 1) * BM, tid);
       __syncthreads();
       start_piece(Q, rb ^ 1);
     }
 
     // ---- finish the piece that just ran
-    KArgs& a = kargs();
+    KArgs& a = fresh_args();
     const auto& Gd = a.g[P.gi];
     if (P.publish) {
-      const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
-          a.sk_slab + (size_t)wl * (TM * TN * 16 * NT), 0, TM * TN * 16 * NT * 4, 0x00020000);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j2 = 0; j2 < TN; ++j2)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x4 v = {acc[i][j2][4 * q], acc[i][j2][4 * q + 1], acc[i][j2][4 * q + 2], acc[i][j2][4 * q + 3]};
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), sr, tid * 16, ((i * TN + j2) * 4 + q) * NT * 16, 0);
-          }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(a.sk_flags + wl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      sk_publish<TM, TN, NT>(a, walk.wl, tid, acc);     // the next worker finishes the tile from these accumulators
     } else {
       // each wave transposes one 32 x 32 accumulator tile at a time through a private 4 KB slice of ring slot 2, so that a
       // lane owns 4 consecutive channels of one pixel (16-B bias / residual reads and stores)
@@ -873,7 +681,7 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) bf3_kernel(const GGArgs a) {
             const size_t idx = (((size_t)ri.x * a.Ho + oy) * a.Wo + ox) * a.Cout + ch;
             f32x4 v = *reinterpret_cast<const f32x4*>(stage + rloc * 32 + c4) + bv;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = act_of(v[e], a.act);
+            for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], a.act);
             if (a.epi != SNTC_EPI_STORE) v = epi_of(v, a.epi, *reinterpret_cast<const f32x4*>(a.res + idx), a.aux, idx);
             *reinterpret_cast<f32x4*>(a.y + idx) = v;
           }

@@ -40,24 +40,9 @@
 #include <type_traits>
 #include "sntc_internal.h"
 #include "gg_tap_rules.h"
+#include "gg_pieces.h"     // the piece walk (which stages of which tile a workgroup computes) and the stream-K hand-off
 
 namespace sntc {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned kOutOfRange = 0x80000000u;   // > any in-range offset: buffers are < 2 GiB (host check)
-constexpr int kSpinLimit = 1 << 22;             // bounded wait on a neighbour's hand-off (~seconds), then the launch is flagged invalid
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-  switch (act) {
-    case SNTC_ACT_RELU: return fmaxf(v, 0.0f);
-    case SNTC_ACT_LEAKY_RELU: return v >= 0.0f ? v : 0.2f * v;
-    case SNTC_ACT_SIGMOID: return 1.0f / (1.0f + expf(-v));
-    default: return v;
-  }
-}
 
 // f(integral_constant<int, HI>), f(HI - 1), ..., f(LO): stops after the first call that returns true; says whether one did
 template <int HI, int LO, class F>
@@ -73,10 +58,6 @@ __device__ __forceinline__ bool first_of_desc(F&& f) {
 __device__ __forceinline__ f32x4 buf_load(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
   const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)soff, 0);
   return __builtin_bit_cast(f32x4, v);
-}
-
-__device__ __forceinline__ void buf_store(__amdgpu_buffer_rsrc_t rsrc, f32x4 v, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, (int)voff, (int)soff, 0);
 }
 
 __device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
@@ -122,24 +103,6 @@ __device__ __forceinline__ float apply_epilogue1(float v, int epi, const float* 
     default: return v;
   }
 }
-
-// The kernel arguments through an OPAQUE pointer to the kernarg segment: loads through it cannot be hoisted out of the
-// persistent tile loop, so a phase that runs once per tile (piece bookkeeping, row table, epilogue) re-reads its few
-// scalars from the scalar cache instead of pinning ~60 SGPRs (and, once those run out, VGPRs) through the K loop.
-typedef const GGArgs __attribute__((address_space(4))) KArgs;
-__device__ __forceinline__ KArgs& fresh_args() {
-  KArgs* kp = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(kp));
-  return *kp;
-}
-
-// One unit of a workgroup's work: stages [k0, k1) of tile (gi, mt, nt).
-struct Piece {
-  int gi, mt, nt, k0, k1;
-  int consume;   // worker whose published accumulators this piece continues (-1: start from zero)
-  int publish;   // 1: the tile is finished by the next worker: leave raw accumulators in sk_slab[self]
-  int split;     // static split-K: index of this K range
-};
 
 // workgroups per CU the register budget must allow (= waves per SIMD for 256-thread workgroups): what the LDS ring admits
 constexpr int gg_waves(int tiles) { return tiles == 1 ? 4 : (tiles <= 3 ? 3 : 2); }
@@ -210,147 +173,15 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
   // ------------------------------------------------------------------------------------------------------
   // the worker's list of pieces
   // ------------------------------------------------------------------------------------------------------
-  // stream-K: [head piece of the LAST tile of the share (published)] [whole tiles] [tail piece of the FIRST tile]
-  int sk_head_t = -1, sk_head_k1 = 0;       // global tile id / end stage of the head piece
-  int sk_tail_t = -1, sk_tail_k0 = 0;
-  int sk_cur = 0, sk_last = -1;             // whole tiles [sk_cur, sk_last]
-  int sk_phase = 0;                         // 0 head, 1 whole tiles, 2 tail, 3 done
-  int wl = 0;
-  if (a.sk) {
-    const int w = blockIdx.x;
-    wl = (w & 7) * (a.nworkers >> 3) + (w >> 3);      // workers on one XCD (b, b + 8, ...) own one contiguous eighth
-    const int u_lo = (int)(a.units * wl / a.nworkers);
-    const int u_hi = (int)(a.units * (wl + 1) / a.nworkers);
-    // tile order: row strip major, then group, then column tile -- every worker's share mixes the groups (their tiles
-    // differ in length, so a group-major order would hand some workers only short, epilogue-heavy tiles) and one strip's
-    // input rows serve all groups while they are hot in L2
-    // COLM (a compile-time twin of the kernel, single-group plans only: round 3 had this as a run-time branch and the branch
-    // moved the whole kernel's register allocation): COLUMN tile outermost, row strips inside (u = nt * ntm * steps + mt * steps
-    // + k, tile id = nt * ntm + mt).  The workers of one XCD own a contiguous eighth of the range, i.e. less than one column
-    // tile of a five-column layer, whose weight rows then stay in that XCD's 4 MB L2 while the strips stream past -- for
-    // layers whose packed weights exceed the L2 (hyper-synthesis 480 -> 640: 11 MB), where the strip-major order streams the
-    // whole matrix through every XCD once per strip.
-    auto locate = [&](int u, int* t, int* k, int* steps) {
-      if constexpr (COLM) {
-        const int st = a.g[0].steps;
-        const int per = a.ntm * st;
-        const int nt = u / per;
-        const int r2 = u - nt * per;
-        const int mt = r2 / st;
-        *t = nt * a.ntm + mt;
-        *k = r2 - mt * st;
-        *steps = st;
-      } else {
-        const int mt = u / a.ups;
-        const int r = u - mt * a.ups;
-        int gi = 0;
-#pragma unroll
-        for (int i = 1; i < kMaxGroups; ++i)
-          if (i < a.ngroups && r >= (int)a.g[i].unit0) gi = i;
-        const int r2 = r - (int)a.g[gi].unit0;
-        const int nt = r2 / a.g[gi].steps;
-        *t = mt * a.tps + a.g[gi].tile0 + nt;
-        *k = r2 - nt * a.g[gi].steps;
-        *steps = a.g[gi].steps;
-      }
-    };
-    if (u_hi > u_lo) {
-      int tF, kF, sF, tL, kL, sL;
-      locate(u_lo, &tF, &kF, &sF);
-      locate(u_hi - 1, &tL, &kL, &sL);
-      sk_cur = tF;
-      sk_last = tL;
-      if (kF > 0) { sk_tail_t = tF; sk_tail_k0 = kF; sk_cur = tF + 1; }
-      if (kL + 1 < sL) { sk_head_t = tL; sk_head_k1 = kL + 1; sk_last = tL - 1; }
-      // host guarantee: a share is at least as long as the longest tile, so head and tail are different tiles
-    } else {
-      sk_phase = 3;
-    }
-  }
-
-  auto tile_of = [&](int t, Piece* p) {          // global tile id -> (group, row strip, column tile): column fastest
-    KArgs& a = fresh_args();
-    if constexpr (COLM) {                        // one group; tile id = nt * ntm + mt
-      const int nt = t / a.ntm;
-      p->gi = 0;
-      p->mt = t - nt * a.ntm;
-      p->nt = nt;
-    } else {
-      const int mt = t / a.tps;
-      const int r = t - mt * a.tps;
-      int gi = 0;
-#pragma unroll
-      for (int i = 1; i < kMaxGroups; ++i)
-        if (i < a.ngroups && r >= a.g[i].tile0) gi = i;
-      p->gi = gi;
-      p->mt = mt;
-      p->nt = r - a.g[gi].tile0;
-    }
-  };
-
-  auto next_piece = [&](Piece* p) -> bool {
-    KArgs& a = fresh_args();
-    if (!a.sk) return false;
-    if (sk_phase == 0) {
-      sk_phase = 1;
-      if (sk_head_t >= 0) {
-        tile_of(sk_head_t, p);
-        p->k0 = 0; p->k1 = sk_head_k1; p->consume = -1; p->publish = 1; p->split = 0;
-        return true;
-      }
-    }
-    if (sk_phase == 1) {
-      if (sk_cur <= sk_last) {
-        tile_of(sk_cur++, p);
-        p->k0 = 0; p->k1 = a.g[p->gi].steps; p->consume = -1; p->publish = 0; p->split = 0;
-        return true;
-      }
-      sk_phase = 2;
-    }
-    if (sk_phase == 2) {
-      sk_phase = 3;
-      if (sk_tail_t >= 0) {
-        tile_of(sk_tail_t, p);
-        p->k0 = sk_tail_k0; p->k1 = a.g[p->gi].steps; p->consume = wl - 1; p->publish = 0; p->split = 0;
-        return true;
-      }
-    }
-    return false;
-  };
-
+  // stream-K: the walk over this worker's share (gg_pieces.h; COLM: the column-major unit order, at compile time); static: one piece
+  PieceWalk<COLM ? kOrderColumn : kOrderStrip> walk;
   Piece P;
-  bool have;
   if (a.sk) {
-    have = next_piece(&P);
+    walk.init(a, blockIdx.x);
+    if (!walk.next(fresh_args(), &P)) return;
   } else {
-    int gi = 0;
-#pragma unroll
-    for (int i = 1; i < kMaxGroups; ++i)
-      if (i < a.ngroups && (int)blockIdx.x >= a.g[i].blk0) gi = i;
-    const int lb0 = blockIdx.x - a.g[gi].blk0;
-    const int split = lb0 % a.ksplit;          // K range of this block (deterministic split-K)
-    const int lb = lb0 / a.ksplit;
-    // XCD-aware tile order: blocks b and b + 8 share an XCD (and its 4 MB L2).  Inside one XCD's sequence the column
-    // tile runs fastest, so the blocks resident on an XCD cover a few row strips x all column tiles.
-    const int ntn = a.g[gi].ntn;
-    const int full = a.ntm & ~7;
-    if (lb < full * ntn) {
-      const int l = lb >> 3;
-      P.mt = (l / ntn) * 8 + (lb & 7);
-      P.nt = l % ntn;
-    } else {                                   // ragged tail: fewer than 8 row strips left
-      const int r = lb - full * ntn, rem = a.ntm - full;
-      P.mt = full + r % rem;
-      P.nt = r / rem;
-    }
-    const int steps = a.g[gi].steps;
-    P.gi = gi;
-    P.k0 = (int)(((long long)split * steps) / a.ksplit);
-    P.k1 = (int)(((long long)(split + 1) * steps) / a.ksplit);
-    P.consume = -1; P.publish = 0; P.split = split;
-    have = true;
+    static_piece(a, blockIdx.x, &P);
   }
-  if (!have) return;
 
   // ------------------------------------------------------------------------------------------------------
   // per-piece loader state
@@ -401,26 +232,6 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
       // branch-free: in-range sums stay below 2^31 (host check); a padding row (a_img = 2^31) or a tap outside the image
       // gets bit 31 and reads zeros from the descriptor's bounds check
       a_off[i] = (a_img[i] + pix) | (ok ? 0u : kOutOfRange);
-    }
-  };
-
-  // rinfo of piece `p` into buffer `rb`; caller synchronises before reading it
-  auto write_rinfo = [&](const Piece& p, int rb) {
-    KArgs& a = fresh_args();
-    int4* rinfo = rinfo_all + rb * BM;
-    const int mbase = p.mt * BM;
-    const int q0y = a.g[p.gi].q0y, q0x = a.g[p.gi].q0x;
-    for (int r = tid; r < BM; r += 256) {
-      const int m = mbase + r;
-      int4 ri = make_int4(0, 0, 0, 0);
-      if (m < a.M) {
-        const int per = a.Qh * a.Qw;
-        const int n = m / per;
-        const int rem = m - n * per;
-        const int qy = rem / a.Qw;
-        ri = make_int4(n, qy + q0y, rem - qy * a.Qw + q0x, 1);   // per-group origin of the macro grid
-      }
-      rinfo[r] = ri;
     }
   };
 
@@ -707,7 +518,7 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
   // ------------------------------------------------------------------------------------------------------
   int rb = 0;                                  // rinfo buffer of the current piece
   Regs R0, R1;
-  write_rinfo(P, rb);
+  write_rinfo<BM, 256>(fresh_args(), P, rinfo_all + rb * BM, tid);
   __syncthreads();
   init_loader(P, rb);
   int dma_issued = 0;                          // DMA: stages of the current piece already on their way (slots 0 ...)
@@ -724,36 +535,7 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
     const int n = P.k1 - P.k0;
     // ---- accumulators: zero, or the previous worker's published partial sums (stream-K continuation)
     if (P.consume >= 0) {
-      if (tid == 0) {
-        int spins = 0;
-        while (__hip_atomic_load(a.sk_flags + P.consume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-          __builtin_amdgcn_s_sleep(8);
-          if (++spins > kSpinLimit) {
-            // a neighbour that never published (it cannot be co-resident: HIP promises neither residency nor dispatch
-            // order): never hang and never take the context down -- flag the launch as invalid and carry on with whatever
-            // the slab holds; the host reads the sticky word at its next synchronisation point (sntc_conv_status), raises,
-            // and can re-run on the static schedule (sntc_conv_set_stream_k(0))
-            __hip_atomic_fetch_or(fresh_args().status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __syncthreads();
-      // slab layout [TN * 4 quads][256 threads][4 floats]: 16 B per lane, 1 KB per wave instruction; addressed through a
-      // buffer descriptor with constant scalar offsets (no per-store 64-bit address registers)
-      const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
-          a.sk_slab + (size_t)P.consume * (TM * TN * 16 * 256), 0, TM * TN * 16 * 256 * 4, 0x00020000);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x4 v = buf_load(sr, (unsigned)tid * 16u, (unsigned)((i * TN + j) * 4 + q) * 4096u);
-            acc[i][j][4 * q] = v[0]; acc[i][j][4 * q + 1] = v[1]; acc[i][j][4 * q + 2] = v[2]; acc[i][j][4 * q + 3] = v[3];
-          }
+      sk_consume<TM, TN, 256>(a, P.consume, tid, acc);
     } else {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -920,12 +702,12 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
 
     // ---- the next piece's first stages go in flight before this piece's results are stored
     Piece Q;
-    const bool more = next_piece(&Q);
+    const bool more = walk.next(fresh_args(), &Q);
     const int qb = rb ^ 1;
     const int4* rinfo = rinfo_all + rb * BM;
     const int m0d = m0, n0d = n0;
     if (more) {
-      write_rinfo(Q, qb);
+      write_rinfo<BM, 256>(fresh_args(), Q, rinfo_all + qb * BM, tid);
       __syncthreads();
       init_loader(Q, qb);
       const int nq = Q.k1 - Q.k0;
@@ -949,26 +731,7 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
     KArgs& a = fresh_args();          // shadows the by-value copy inside this phase
     const auto& Gd = a.g[P.gi];
     if (P.publish) {
-      // stream-K hand-off, producer side (cdna_hip_programming.md Guideline 16): plain stores, every wave drains its
-      // stores, workgroup barrier, ONE agent-scope release, then the flag
-      const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
-          a.sk_slab + (size_t)wl * (TM * TN * 16 * 256), 0, TM * TN * 16 * 256 * 4, 0x00020000);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-            buf_store(sr, v, (unsigned)tid * 16u, (unsigned)((i * TN + j) * 4 + q) * 4096u);
-          }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(a.sk_flags + wl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      sk_publish<TM, TN, 256>(a, walk.wl, tid, acc);     // the next worker finishes the tile from these accumulators
     } else if (a.ksplit > 1) {
       // split-K: raw partial sums go to slab[group][split][m][col]; gg_reduce_kernel adds the splits in a
       // fixed order and applies bias / activation / epilogue, so the result does not depend on scheduling.

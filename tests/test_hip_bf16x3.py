@@ -16,6 +16,7 @@ from oracle import ops_np as O
 pytestmark = pytest.mark.gpu
 
 RESBLOCK_DIGESTS = json.loads((Path(__file__).resolve().parent / "golden" / "resblock_bf16x3.json").read_text())["sha256"]
+PIECE_DIGESTS = json.loads((Path(__file__).resolve().parent / "golden" / "gg_pieces_digests.json").read_text())["presplit"]
 
 
 def dev_t(a, dev):
@@ -119,6 +120,48 @@ def test_presplit_kernel_against_float64(kind, k, s, cin, cout, n, h, w, act, ep
     assert torch.equal(alone, outs[0][:1])
     with pytest.raises(ValueError):
         ps(xd)                                                      # fp32 input to a pre-split plan: refused, not reinterpreted
+
+
+# The pre-split kernel has no external bit reference (its schedules are compared with each other above): the output bytes of two
+# launches whose stream-K walk cuts tiles between workers, recorded with the library of the commit before the walk and the hand-off
+# moved to csrc/gg_pieces.h (tests/golden/gg_pieces_digests.json).
+PIECE_CASES = {  # kind, k, s, cin, cout, n, h, w
+    "convT-5-2-32-48": ("convT", 5, 2, 32, 48, 2, 80, 80),      # four phase groups of 18 / 12 / 12 / 8 stages: ~136 workers on ~200 tiles
+    "conv-1-1-48-64": ("conv", 1, 1, 48, 64, 2, 160, 120),      # 3 stages per tile, 150 tiles: ragged shares
+}
+
+
+@pytest.mark.parametrize("name", list(PIECE_CASES))
+def test_presplit_schedules_give_the_recorded_bytes(name, dev):
+    """Variants 11, 12, 13, static and forced stream-K (which really is a smaller launch), patch staging on and off: all twelve
+    outputs have the one recorded SHA-256.  Inputs from numpy's generator, fixed seeds."""
+    from shallow_ntc_amd import ops
+    kind, k, s, cin, cout, n, h, w = PIECE_CASES[name]
+    rng = np.random.default_rng(2024 + k + cin + cout)
+    x = rng.standard_normal((n, h, w, cin)).astype(np.float32)
+    wk = (rng.standard_normal((k, k, cout, cin) if kind == "convT" else (k, k, cin, cout)) * 0.1).astype(np.float32)
+    b = rng.standard_normal(cout).astype(np.float32)
+    ps = ops.ConvPlan(kind, dev_t(wk, dev), dev_t(b, dev), s, "relu", bf16x3="presplit")
+    xs = ops.split3(dev_t(x, dev))
+    got = {}
+    for variant in (11, 12, 13):
+        ps.set_tile(variant)
+        for halo in (True, False):
+            ps.set_stream_k(False, halo=halo)
+            v_st, nb_static = ps.launch_info(n, h, w)
+            got[variant, "static", halo] = hashlib.sha256(ps(xs).cpu().numpy().tobytes()).hexdigest()
+            ps.set_stream_k(True, force=True, halo=halo)
+            v_sk, nb_sk = ps.launch_info(n, h, w)
+            print("LAUNCH", name, variant, halo, "static", nb_static, "stream-K", nb_sk)
+            assert v_st == variant and v_sk == variant and nb_sk < nb_static, (variant, nb_sk, nb_static)   # the workers really run it
+            got[variant, "stream-K", halo] = hashlib.sha256(ps(xs).cpu().numpy().tobytes()).hexdigest()
+    torch.cuda.synchronize()
+    ops.check_conv_status()
+    print("DIGEST presplit", name, sorted(set(got.values())))
+    want = PIECE_DIGESTS.get(name)
+    assert len(got) == 12 and all(d == want for d in got.values()), (
+        {k_: d for k_, d in got.items() if d != want}, f"recorded {want}: re-record tests/golden/gg_pieces_digests.json only with a "
+        "deliberate change of the split arithmetic")
 
 
 def test_presplit_plan_limits(dev):

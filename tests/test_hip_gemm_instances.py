@@ -19,6 +19,7 @@ How each instance is reached (csrc/conv_plan.hip, schedule() resolves a launch t
   * bf16 x 3: bf16x3=True plans, variants 2 and 4 only (any other forced variant has no instance: SntcError).
 """
 import ctypes as C
+import hashlib
 import json
 import re
 import zlib
@@ -369,6 +370,9 @@ SK_CASES = [  # cin, cout, prologue, epilogue     (1x1, n = 2, 271 x 263: M = 14
     (33, 33, 1, 3),
 ]
 SK_N, SK_H, SK_W = 2, 271, 263
+# SHA-256 of the heuristic's float32 output bytes per case, recorded with the library of the commit before the piece walk moved to
+# csrc/gg_pieces.h: every instance below is torch.equal to that output, so one comparison pins them all to those bits
+SK_DIGESTS = json.loads((ROOT / "tests" / "golden" / "gg_pieces_digests.json").read_text())["fp32_sk_cases"]
 
 
 @gpu
@@ -390,6 +394,10 @@ def test_every_variant_and_schedule_on_a_stream_k_launch(case, dev):
     workers = {}
     with _state(plan):
         y0 = plan(xd, res=res).clone()
+        got = hashlib.sha256(y0.cpu().numpy().tobytes()).hexdigest()
+        print("DIGEST fp32_sk_cases", "-".join(map(str, case)), got)
+        assert got == SK_DIGESTS.get("-".join(map(str, case))), (got, "recorded in tests/golden/gg_pieces_digests.json: re-record only "
+                                                                      "with a deliberate change of the fp32 arithmetic")
         _within(y0, ref)
         for v in VARIANTS:
             plan.set_tile(v)

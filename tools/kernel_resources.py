@@ -7,7 +7,7 @@ code size of the fp32 instances that carry the decode (round 3 lost 8 % to exact
     python tools/kernel_resources.py --write    # ... and rewrite profiles/kernel_resources.json (commit it with the change)
     python tools/kernel_resources.py --check    # exit 1 if an instance differs from the committed table (tests/test_abi_and_host.py)
 
-No GPU needed (hipcc cross-compiles); the four sources take about three minutes."""
+No GPU needed (hipcc cross-compiles); the listed sources take about five minutes."""
 import json
 import re
 import subprocess
@@ -29,6 +29,18 @@ WATCH = {
         "gg 64x64": "gg_kernelILi1ELi1ELi2ELi2ELb1ELb0ELb0ELb0ELi0ELb0ELb0EE",
     },
     "gg_inst_fuse.hip": {"gg fused ResidualBlock tail": "gg_kernelILi1ELi3ELi4ELi1ELb1ELb0ELb0ELb0ELi0ELb1ELb0EE"},
+    "gg_inst_dma.hip": {
+        "gg 128x128 direct-to-LDS": "gg_kernelILi2ELi2ELi2ELi2ELb1ELb0ELb0ELb1ELi0ELb0ELb0EE",
+        "gg 64x64 direct-to-LDS, deep ring": "gg_kernelILi1ELi1ELi2ELi2ELb1ELb0ELb0ELb1ELi8ELb0ELb0EE",
+    },
+    "bf3_gemm.hip": {
+        "bf3 256x256 (variant 11)": "bf3_kernelILi4ELi2ELi2ELi4ELb0ELb0EE",
+        "bf3 256x256 (variant 11), patch staging": "bf3_kernelILi4ELi2ELi2ELi4ELb1ELb0EE",
+        "bf3 256x128 (variant 12)": "bf3_kernelILi4ELi2ELi2ELi2ELb0ELb0EE",
+        "bf3 256x128 (variant 12), patch staging, deep": "bf3_kernelILi4ELi2ELi2ELi2ELb1ELb1EE",
+        "bf3 256x192 (variant 13)": "bf3_kernelILi4ELi2ELi2ELi3ELb0ELb0EE",
+        "bf3 256x192 (variant 13), patch staging": "bf3_kernelILi4ELi2ELi2ELi3ELb1ELb0EE",
+    },
     "rb_fused.hip": {"rb_kernel<192>": "rb_kernelILi192EE"},
     "rb_fused_bf3.hip": {"rb3_kernel<192>": "rb3_kernelILi192EE"},
     "syn_fused.hip": {"syn_kernel<24, true>": "syn_kernelILi24ELb1EE", "syn_kernel<12, false>": "syn_kernelILi12ELb0EE",
