@@ -577,22 +577,77 @@ def _decode_setup(shape, out_dtype, payload, lens_h, tables, segments, lanes, ba
     return n, E, segments, lanes, offsets, out, bad, dec
 
 
-def _raise_if_bad(bad, streams):
-    nbad = int(bad.item())
-    if nbad:
-        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {streams} rANS streams did not terminate cleanly")
+def _raise_if_bad(nbad, streams, nres=None):
+    """The one refusal of a corrupt payload: ``nbad`` of ``streams`` rANS streams ended in a state no encoder leaves (host ints,
+    read back where the caller synchronises anyway); ``nres`` (a layered file): the residual values outside what an encoder writes."""
+    if nbad or nres:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {streams} rANS streams did not terminate cleanly" +
+                             ("" if nres is None else f", {nres} residual values lie outside what an encoder writes"))
+
+
+def pack_upload(arrays, device):
+    """ONE upload for several host arrays: packed in the order given into one uint8 buffer, each at an offset aligned to its item
+    size (padded where the order does not give that), one copy to ``device``.  -> (the buffer on the device -- what a caller
+    names to ``ops.fork`` where a lane reads the views --, the arrays as flat device tensors of their dtypes: views of it)."""
+    arrays = [np.asarray(a).reshape(-1) for a in arrays]
+    at, pos = [], 0
+    for a in arrays:
+        pos += -pos % a.itemsize
+        at.append(pos)
+        pos += a.nbytes
+    host = np.empty(pos, np.uint8)
+    for a, o in zip(arrays, at):
+        assert o % a.itemsize == 0
+        host[o:o + a.nbytes].view(a.dtype)[:] = a
+    up = torch.from_numpy(host).to(device) if pos else torch.empty(0, dtype=torch.uint8, device=device)      # (numpy's empty: stride 0)
+    return up, [up[o:o + a.nbytes].view(torch.from_numpy(np.empty(0, a.dtype)).dtype) for a, o in zip(arrays, at)]
+
+
+def finish_streams(jobs):
+    """The two read-backs that end every encode, for ALL blobs at once: ``jobs`` = per blob the (scratch, lens) groups of its
+    ``rans_encode_launch`` calls -> per blob, per group, (lens on the host int64, the group's streams packed back to back as
+    int16 words on the host).  The stream lengths come back in one copy, the packed payloads in another; then
+    ``ops.check_conv_status()``: the copies synchronised the stream, a flagged stream-K launch raises here, not a wrong file."""
+    groups = [g for job in jobs for g in job]
+    cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)
+    lens_h = cat([lens for _, lens in groups]).cpu().numpy().astype(np.int64)                                   # read-back 1 of 2
+    cuts = np.cumsum([0] + [lens.numel() for _, lens in groups])
+    lens_h = [lens_h[a:b] for a, b in zip(cuts, cuts[1:])]
+    words = cat([rans_encode_finish(s, lens, lh) for (s, lens), lh in zip(groups, lens_h)]).cpu().numpy()        # read-back 2 of 2
+    ops.check_conv_status()
+    cuts = np.cumsum([0] + [int(lh.sum()) for lh in lens_h])
+    done = iter([(lh, words[a:b]) for lh, a, b in zip(lens_h, cuts, cuts[1:])])
+    return [[next(done) for _ in job] for job in jobs]
+
+
+def _compress_many(codec, xs):
+    """``compress_many`` of both codecs: ``codec._launch(x)`` per batch, each on a lane of its own (``ops.lanes``), its stream
+    groups handed to the caller's stream, ``codec._finish`` for the set."""
+    m = codec.m
+    xs = [m._as_device_images(x) for x in xs]
+    if not xs:
+        return []
+    with torch.cuda.device(m.device):
+        main, lanes = ops.lanes(len(xs), m.device)
+        jobs = []
+        for st, x in zip(lanes, xs):
+            with ops.fork(main, st, reads=(x,)):
+                jobs.append(codec._launch(x))
+        for st, j in zip(lanes, jobs):
+            ops.join(main, st, made=[t for g in j["groups"] for t in g])
+        return codec._finish(jobs)
 
 
 def rans_decode(payload, lens_h, table_ids, shape, tables: DeviceTables, segments=None, lanes=None, bad=None, offsets=None):
     """-> int32 values of ``shape`` [n, ...]; raises on a malformed stream.  ``bad`` (an int32 device tensor [1]): count the
-    streams that did not terminate cleanly there instead of reading the count back here -- the caller checks it where it
+    malformed streams there instead of reading the count back here -- the caller checks it where it
     synchronises anyway (a decoder that keeps several batches in flight).  The decoder's start tables are used where
     ``DeviceTables`` could place them (``tables.dec``); else the binary search of ``cdf``."""
     n, E, segments, lanes, offsets, values, count, dec = _decode_setup(shape, torch.int32, payload, lens_h, tables, segments, lanes, bad, offsets)
     capi.call("sntc_rans_decode", _p(payload), _p(offsets), _p(table_ids), n, E, segments, lanes, _p(tables.cdf), _p(tables.meta),
               tables.ntables, tables.total, *dec, _p(values), _p(count), ops._stream())
     if bad is None:
-        _raise_if_bad(count, n * segments)
+        _raise_if_bad(int(count.item()), n * segments)
     return values
 
 
@@ -646,7 +701,7 @@ def rans_decode_channels(payload, lens_h, shape, tables: DeviceTables, segments=
     capi.call("sntc_rans_decode_channels", _p(payload), _p(offsets), n, E, c, segments, lanes, _p(tables.cdf), _p(tables.meta),
               tables.total, *dec, _p(y_hat), _p(count), ops._stream())
     if bad is None:
-        _raise_if_bad(count, n * segments)
+        _raise_if_bad(int(count.item()), n * segments)
     return y_hat
 
 
@@ -1323,41 +1378,24 @@ class Codec:
         zi, ztid, sym, ytid, _ = self._symbols(z, y, grid, pre)
         sz, sy = _segments(zi[0].numel()), _segments(sym[0].numel())
         lz, ly = _lanes(-(-zi[0].numel() // sz)), _lanes(-(-sym[0].numel() // sy))
-        zs, zlen = rans_encode_launch(zi, ztid, self.z_tables, sz, lz)
-        ys, ylen = rans_encode_launch(sym, ytid, self.y_tables, sy, ly)
-        return dict(n=n, H=H, W=W, z=z, y=y, sz=sz, sy=sy, lz=lz, ly=ly, zs=zs, zlen=zlen, ys=ys, ylen=ylen, grid=grid)
+        dims = (y.shape[-1], z.shape[-1], z.shape[1], z.shape[2], y.shape[1], y.shape[2])
+        groups = [rans_encode_launch(zi, ztid, self.z_tables, sz, lz), rans_encode_launch(sym, ytid, self.y_tables, sy, ly)]
+        return dict(n=n, H=H, W=W, dims=dims, sz=sz, sy=sy, lz=lz, ly=ly, groups=groups, grid=grid)
+
+    def _launch(self, x):
+        """analysis -> ``_launch_latents`` on the unit grid."""
+        lat = self.m.infer_latent_rvs(x)
+        return self._launch_latents(lat.uq[0].loc, lat.uq[1].loc, x.shape[1:3], StepGrid("unit", x.shape[0]))
 
     def _finish(self, jobs):
-        """Launched jobs -> their blobs: the stream lengths of ALL jobs come back in one copy, the packed payloads in another.
-        A job of ``transcode_many`` carries zlen = None: its z streams are not coded here but copied -- ``zl`` their lengths,
-        ``zbytes`` their words as the source blob holds them, ``dims`` the header's (C, Cz, hz, wz, h, w)."""
-        m = self.m
-        lens_h = torch.cat([t for j in jobs for t in (j["zlen"], j["ylen"]) if t is not None]).cpu().numpy().astype(np.int64)   # read-back 1 of 2
-        pays, o = [], 0
-        for j in jobs:
-            if j["zlen"] is not None:
-                nz = j["zlen"].numel()
-                j["zl"] = lens_h[o:o + nz]
-                o += nz
-                pays.append(rans_encode_finish(j["zs"], j["zlen"], j["zl"]))
-            ny = j["ylen"].numel()
-            j["yl"] = lens_h[o:o + ny]
-            o += ny
-            pays.append(rans_encode_finish(j["ys"], j["ylen"], j["yl"]))
-        words = torch.cat(pays).cpu().numpy()                                                                    # read-back 2 of 2
-        ops.check_conv_status()       # the copies synchronised the stream: a flagged stream-K launch raises here, not a wrong file
-        out, o = [], 0
-        for j in jobs:
-            copied = j["zlen"] is None
-            zw, yw = 0 if copied else int(j["zl"].sum()), int(j["yl"].sum())
-            if copied:
-                dims = j["dims"]
-            else:
-                z, y = j["z"], j["y"]
-                dims = (y.shape[-1], z.shape[-1], z.shape[1], z.shape[2], y.shape[1], y.shape[2])
-            fields = (ARITH[m._precision], j["n"], j["H"], j["W"], dims, j["sz"], j["sy"], j["lz"], j["ly"], j["zl"], j["yl"])
-            out.append(j["grid"].pack(*fields) + (j["zbytes"] if copied else b"") + words[o:o + zw + yw].tobytes())
-            o += zw + yw
+        """Launched jobs -> their blobs (``finish_streams``: two read-backs for all of them).  ``dims``: the header's (C, Cz, hz,
+        wz, h, w).  A job of ``transcode_many`` has one coded group, y: its z streams are copied -- ``copied`` = (their lengths,
+        their words) as the source blob holds them."""
+        out = []
+        for j, done in zip(jobs, finish_streams([j["groups"] for j in jobs])):
+            (zl, zwords), (yl, ywords) = [j["copied"]] + done if "copied" in j else done
+            fields = (ARITH[self.m._precision], j["n"], j["H"], j["W"], j["dims"], j["sz"], j["sy"], j["lz"], j["ly"], zl, yl)
+            out.append(j["grid"].pack(*fields) + zwords.tobytes() + ywords.tobytes())
         return out
 
     def compress_latents(self, z_loc, y_loc, image_hw, step=None, step_offsets=None) -> bytes:
@@ -1543,26 +1581,7 @@ class Codec:
         ``compress`` per batch returns.  The batches' transforms and entropy-coding launches run side by side on the library's
         side streams; the stream lengths of ALL batches come back in one copy, the packed payloads in another -- two host
         synchronisations for the set instead of two per batch."""
-        m = self.m
-        xs = [m._as_device_images(x) for x in xs]
-        if not xs:
-            return []
-        with torch.cuda.device(m.device):
-            main = torch.cuda.current_stream()
-            side = ops.side_streams(len(xs), m.device) if len(xs) > 1 and not torch.cuda.is_current_stream_capturing() else [main] * len(xs)
-            jobs = []
-            for st, x in zip(side, xs):
-                if st is not main:
-                    st.wait_stream(main)
-                with torch.cuda.stream(st):
-                    lat = m.infer_latent_rvs(x)
-                    jobs.append(dict(self._launch_latents(lat.uq[0].loc, lat.uq[1].loc, x.shape[1:3], StepGrid("unit", x.shape[0])), st=st))
-            for j in jobs:
-                if j["st"] is not main:
-                    main.wait_stream(j["st"])
-                    for t in (j["zs"], j["zlen"], j["ys"], j["ylen"]):
-                        t.record_stream(main)
-            return self._finish(jobs)
+        return _compress_many(self, xs)
 
     def _parse(self, blob: bytes):
         """Header and stream lengths of one blob, checked against THIS model: nothing later trusts the header."""
@@ -1585,7 +1604,8 @@ class Codec:
         stream-K convolution needs every one of its workers resident (round 4 measured what happens when they meet: groups of one
         blob's images pipelined against each other's stream-K convolutions, 9.5 -> 10.9 / 12.7 / 17.6 ms with 2 / 3 / 4 groups),
         so only the FIRST hyper-synthesis -- which meets no decoding wave -- keeps stream-K; the convolutions that may run beside
-        decoding waves take the static schedules (``ops.static_schedules``; same bits)."""
+        decoding waves take the static schedules (``ops.static_schedules``; same bits).  Everything up to the latents' decode is
+        ``_decode_front``, shared with ``transcode_many``; the syntheses, the residual layers and the final check are here."""
         m = self.m
         if not blobs:
             return []
@@ -1599,123 +1619,109 @@ class Codec:
                     layers[k]["blob"] = b
         nlayers = sum(l is not None for l in layers)
         heads = [self._parse(b) for b in blobs]
-        dev = m.device
-        with torch.cuda.device(dev):
-            main = torch.cuda.current_stream()
-            side = self._side_streams(len(blobs)) if len(blobs) > 1 and not torch.cuda.is_current_stream_capturing() else [main] * len(blobs)
-            # one counter per entropy-decoding launch (the launch zeroes its own), ONE read-back for everything at the end: the
-            # chain z symbols -> hyper-synthesis -> y symbols -> synthesis is enqueued without the host waiting in between
-            # (a residual layer adds two behind the others: its streams', and the out-of-range count of sntc_residual_apply)
-            bad = torch.zeros((2 * (len(blobs) + nlayers),), dtype=torch.int32, device=dev)
-            pay, offd = self._upload_streams(blobs, heads)
-            # v5 / v7: every blob's step tensors or map go up here too, before anything is enqueued; they are read on the caller's
-            # stream only
-            grids = [hd["grid"] for hd in heads]
-            for grid in grids:
-                grid.on(dev)
-            zis = self._decode_hyper_latents(heads, pay, offd, bad, side, main)
-            # From here on the blobs are PIPELINED, largest first: a blob's latents decode on its side stream while the caller's
-            # stream runs the next blob's hyper-synthesis, and its synthesis runs while the later blobs' latents decode.  The first
-            # blob's hyper-synthesis meets no decoding wave and keeps its stream-K launches; every convolution after it may run
-            # beside decoding waves and takes the static schedules (ops.static_schedules: same bits).
-            piped = PIPELINE_BLOBS and len(heads) > 1 and side[0] is not main
-            order = sorted(range(len(heads)), key=lambda k: -(heads[k]["n"] * heads[k]["h"] * heads[k]["w"])) if piped else list(range(len(heads)))
-            hypers, syms, tidl = [None] * len(heads), [None] * len(heads), [None] * len(heads)
-
-            def launch_latents(k):
-                hd, st = heads[k], side[k]
-                if st is not main:
-                    st.wait_stream(main)
-                with torch.cuda.stream(st):
-                    syms[k] = rans_decode(pay[k][1], hd["yl"], tidl[k], (hd["n"], hd["h"], hd["w"], hd["c"]), self.y_tables, hd["sy"], hd["ly"],
-                                          bad=bad[2 * k + 1:2 * k + 2], offsets=offd[k][1])
-                if st is not main:
-                    tidl[k].record_stream(st)
-
+        with torch.cuda.device(m.device):
+            # (a residual layer adds two counters behind the others: its streams', and the out-of-range count of sntc_residual_apply)
+            f = self._decode_front(blobs, heads, counters=2 * nlayers)
+            main, lanes, bad, order, piped = f["main"], f["lanes"], f["bad"], f["order"], f["piped"]
+            # A blob's synthesis runs while the later blobs' latents decode: every synthesis but the last may run beside decoding
+            # waves and takes the static schedules.  A/B (PIPELINE_BLOBS = False): every blob's latents first, then the syntheses
+            for k in ([] if piped else order):
+                ops.join(main, lanes[k])
+            out = [None] * len(heads)
             for i, k in enumerate(order):
                 hd = heads[k]
-                with ops.static_schedules(piped and i > 0):
-                    hyper = m._hyper_synthesis(int_to_float(zis[k]))
-                if tuple(hyper.shape) != (hd["n"], hd["h"], hd["w"], 2 * hd["c"]):
-                    raise capi.SntcError(capi.ERR_BAD_SHAPE, f"hyper-synthesis output {tuple(hyper.shape)} does not match the latents "
-                                         f"{(hd['n'], hd['h'], hd['w'], hd['c'])}")
-                hypers[k] = hyper
-                tidl[k] = grids[k].table_ids(scale_table_ids(hyper))
-                if piped:
-                    launch_latents(k)
-            if not piped:                    # A/B (PIPELINE_BLOBS = False), round 4's schedule: every hyper-synthesis, then every blob's
-                for k in order:              # latents side by side, then the syntheses
-                    launch_latents(k)
-            out = [None] * len(heads)
-            if not piped:                    # A/B (PIPELINE_BLOBS = False): every blob's latents first, then the syntheses
-                for k in order:
-                    if side[k] is not main:
-                        main.wait_stream(side[k])
-            for i, k in enumerate(order):
-                hd, st = heads[k], side[k]
-                if st is not main:
-                    main.wait_stream(st)
-                    syms[k].record_stream(main)
+                ops.join(main, lanes[k], made=(f["syms"][k],))
                 with ops.static_schedules(piped and i + 1 < len(order)):
-                    y_hat = grids[k].dequant(syms[k], hypers[k], m._synthesis.takes_s3(hd["h"], hd["w"]))
+                    y_hat = hd["grid"].dequant(f["syms"][k], f["hypers"][k], m._synthesis.takes_s3(hd["h"], hd["w"]))
                     out[k] = m._pixels(y_hat, (hd["H"], hd["W"]))
             if nlayers:
-                self._apply_layers(layers, out, bad[2 * len(blobs):], main)
+                self._apply_layers(layers, out, bad[2 * len(blobs):])
             nbad = int(bad.sum().item())                           # synchronises the stream
-            if nbad:
-                total = sum(hd["n"] * (hd["sz"] + hd["sy"]) for hd in heads)
-                if nlayers:
-                    counts = bad.cpu().numpy()
-                    nres = int(counts[2 * len(blobs) + 1::2].sum())
-                    total += sum(l["n"] * l["segments"] for l in layers if l is not None)
-                    raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad - nres} of {total} rANS streams did not terminate "
-                                         f"cleanly, {nres} residual values lie outside what an encoder writes")
-                raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {total} rANS streams did not terminate cleanly")
+            total = sum(hd["n"] * (hd["sz"] + hd["sy"]) for hd in heads) + sum(l["n"] * l["segments"] for l in layers if l is not None)
+            nres = int(bad[2 * len(blobs) + 1::2].sum().item()) if nbad and nlayers else None
+            _raise_if_bad(nbad - (nres or 0), total, nres)
             ops.check_conv_status()       # wrong pixels never leave without an error
             return out
 
-    def _apply_layers(self, layers, out, bad, main):
+    def _decode_front(self, blobs, heads, counters=0):
+        """The front of ``decompress_many`` and ``transcode_many``: parsed ``heads`` of ``blobs`` -> per blob the y symbols, with
+        their decode IN FLIGHT on the blob's lane -- the caller joins lanes[k], naming syms[k], when it consumes blob k, in
+        ``order`` --, the hyper-synthesis output and the base table ids (``scale_table_ids``), as a dict of lists indexed by blob
+        (+ main, lanes, bad, order, piped, zis).  Everything the blobs need goes up first (``pack_upload``: ONE copy for all words
+        and stream offsets; v5 / v7: each grid's step tensors or map, read on the caller's stream only), then nothing waits for
+        the host: all z decode side by side and are joined; then the blobs are PIPELINED, largest first (``order``): a blob's
+        latents decode on its lane while the caller's stream runs the next blob's hyper-synthesis.  The first hyper-synthesis
+        meets no decoding wave and keeps its stream-K launches; every convolution after it may run beside decoding waves and
+        takes the static schedules (``ops.static_schedules``: same bits).  A/B (``PIPELINE_BLOBS`` = False), round 4's schedule:
+        every hyper-synthesis, then every blob's latents side by side.
+        ``bad``: one counter per entropy-decoding launch (the launch zeroes its own) -- blob k's z at 2 k, its y at 2 k + 1, then
+        ``counters`` more for the caller -- for ONE read-back where the caller synchronises anyway."""
+        m, dev, nb = self.m, self.m.device, len(heads)
+        main, lanes = ops.lanes(nb, dev)
+        bad = torch.zeros((2 * nb + counters,), dtype=torch.int32, device=dev)
+        offs = [np.concatenate([[0], np.cumsum(hd[f])]).astype(np.int64) for hd in heads for f in ("zl", "yl")]
+        words = [np.frombuffer(b, "<i2", nw, at) for b, hd in zip(blobs, heads)
+                 for nw, at in ((hd["zw"], hd["pos"]), (hd["yw"], hd["pos"] + 2 * hd["zw"]))]
+        up, views = pack_upload(offs + words, dev)
+        offd, pay = views[:2 * nb], views[2 * nb:]
+        for hd in heads:
+            hd["grid"].on(dev)
+        zis = []
+        for k, (hd, st) in enumerate(zip(heads, lanes)):
+            shape = (hd["n"], hd["hz"], hd["wz"], hd["cz"])
+            with ops.fork(main, st, reads=(up, bad)):
+                zis.append(rans_decode(pay[2 * k], hd["zl"], channel_table_ids(shape, dev), shape, self.z_tables, hd["sz"], hd["lz"],
+                                       bad=bad[2 * k:2 * k + 1], offsets=offd[2 * k]))
+        for st, zi in zip(lanes, zis):
+            ops.join(main, st, made=(zi,))
+        piped = PIPELINE_BLOBS and len(set(lanes)) > 1             # the blobs have streams of their own
+        order = sorted(range(nb), key=lambda k: -(heads[k]["n"] * heads[k]["h"] * heads[k]["w"])) if piped else list(range(nb))
+        hypers, bases, tids, syms = [None] * nb, [None] * nb, [None] * nb, [None] * nb
+
+        def launch_latents(k):
+            hd = heads[k]
+            with ops.fork(main, lanes[k], reads=(up, bad, tids[k])):
+                syms[k] = rans_decode(pay[2 * k + 1], hd["yl"], tids[k], (hd["n"], hd["h"], hd["w"], hd["c"]), self.y_tables, hd["sy"],
+                                      hd["ly"], bad=bad[2 * k + 1:2 * k + 2], offsets=offd[2 * k + 1])
+
+        for i, k in enumerate(order):
+            hd = heads[k]
+            with ops.static_schedules(piped and i > 0):
+                hypers[k] = m._hyper_synthesis(int_to_float(zis[k]))
+            if tuple(hypers[k].shape) != (hd["n"], hd["h"], hd["w"], 2 * hd["c"]):
+                raise capi.SntcError(capi.ERR_BAD_SHAPE, f"hyper-synthesis output {tuple(hypers[k].shape)} does not match the latents "
+                                     f"{(hd['n'], hd['h'], hd['w'], hd['c'])}")
+            bases[k] = scale_table_ids(hypers[k])
+            tids[k] = hd["grid"].table_ids(bases[k])
+            if piped:
+                launch_latents(k)
+        for k in ([] if piped else order):
+            launch_latents(k)
+        return dict(main=main, lanes=lanes, bad=bad, order=order, piped=piped, zis=zis, syms=syms, hypers=hypers, bases=bases)
+
+    def _apply_layers(self, layers, out, bad):
         """The residual layers of ``decompress_many``: ``layers[k]`` = ``split_residual``'s info of blob k or None, ``out[k]`` its
-        decoded base picture, already enqueued on ``main``.  ONE upload for every layer's words, stream offsets and choices; per
-        layer, on a pooled side stream, ``residual_table_ids`` -> ``rans_decode`` -> ``residual_apply`` replaces out[k]; layer j's
-        bad-stream count goes to bad[2 j], its out-of-range count to bad[2 j + 1].  The layers start after the last synthesis
-        was enqueued: their decoding waves run side by side with each other, never beside a stream-K convolution."""
-        dev = self.m.device
+        decoded base picture, already enqueued on the caller's stream.  ONE upload for every layer's words, stream offsets and
+        choices; per layer, on a pooled lane (a single layer too), ``residual_table_ids`` -> ``rans_decode`` -> ``residual_apply``
+        replaces out[k]; layer j's bad-stream count goes to bad[2 j], its out-of-range count to bad[2 j + 1].  The layers start
+        after the last synthesis was enqueued: their decoding waves run side by side with each other, never beside a stream-K
+        convolution."""
         ks = [k for k, l in enumerate(layers) if l is not None]
-        offs = [np.concatenate([[0], np.cumsum(layers[k]["lens"])]).astype(np.int64) for k in ks]
-        noff, nword = sum(len(o) for o in offs), sum(layers[k]["words"] for k in ks)
-        host = np.empty(8 * noff + 2 * nword + sum(layers[k]["choice"].size for k in ks), np.uint8)
-        host[:8 * noff].view(np.int64)[:] = np.concatenate(offs)
-        host[8 * noff:8 * noff + 2 * nword].view(np.int16)[:] = np.concatenate([np.frombuffer(layers[k]["blob"], "<i2", layers[k]["words"],
-                                                                                              layers[k]["pos"]) for k in ks])
-        host[8 * noff + 2 * nword:] = np.concatenate([layers[k]["choice"].reshape(-1) for k in ks])
-        up = torch.from_numpy(host).to(dev)
-        off_d, word_d, choice_d = up[:8 * noff].view(torch.int64), up[8 * noff:8 * noff + 2 * nword].view(torch.int16), up[8 * noff + 2 * nword:]
-        side = [main] * len(ks) if torch.cuda.is_current_stream_capturing() else self._side_streams(len(ks))
-        o = wpos = cpos = 0
-        for j, (k, st) in enumerate(zip(ks, side)):
-            l, base = layers[k], out[k]
+        ls = [layers[k] for k in ks]
+        up, views = pack_upload([np.concatenate([[0], np.cumsum(l["lens"])]).astype(np.int64) for l in ls] +
+                                [np.frombuffer(l["blob"], "<i2", l["words"], l["pos"]) for l in ls] + [l["choice"] for l in ls], self.m.device)
+        main, lanes = ops.lanes(len(ks), self.m.device, alone=True)
+        for j, (k, l, st) in enumerate(zip(ks, ls, lanes)):
+            base, (off_d, word_d, choice_d) = out[k], views[j::len(ks)]
             shape = (l["n"], l["H"], l["W"], RESIDUAL_CHANNELS)
             if tuple(base.shape) != shape:
                 raise capi.SntcError(capi.ERR_BAD_SHAPE, f"decoded base picture {tuple(base.shape)} does not match the residual layer's {shape}")
-            choice = choice_d[cpos:cpos + l["choice"].size].view(l["n"], -1)
-            if st is not main:
-                st.wait_stream(main)
-            with torch.cuda.stream(st):
-                ids = residual_table_ids(base, choice)
-                q = rans_decode(word_d[wpos:wpos + l["words"]], l["lens"], ids, shape, self.y_tables, l["segments"], l["lanes"],
-                                bad=bad[2 * j:2 * j + 1], offsets=off_d[o:o + len(offs[j])])
+            with ops.fork(main, st, reads=(base, up, bad)):
+                ids = residual_table_ids(base, choice_d.view(l["n"], -1))
+                q = rans_decode(word_d, l["lens"], ids, shape, self.y_tables, l["segments"], l["lanes"], bad=bad[2 * j:2 * j + 1], offsets=off_d)
                 out[k], _ = residual_apply(base, q, l["max_error"], count=bad[2 * j + 1:2 * j + 2])
-            if st is not main:
-                for t in (base, up):
-                    t.record_stream(st)
-            o += len(offs[j])
-            wpos += l["words"]
-            cpos += l["choice"].size
-        for k, st in zip(ks, side):
-            if st is not main:
-                main.wait_stream(st)
-                out[k].record_stream(main)
+        for k, st in zip(ks, lanes):
+            ops.join(main, st, made=(out[k],))
 
     def _refuse_layered(self, blobs, what):
         for b in blobs:
@@ -1792,46 +1798,6 @@ class Codec:
         bits = np.stack([residual_choice(h, self.y_tables.host)[1] / float(COST_UNIT) + 32.0 * segments * lanes for h in hists], axis=1)
         return bits if many else bits[:, 0]
 
-    def _upload_streams(self, blobs, heads):
-        """ONE upload for every blob's words and stream offsets (int64 offsets first, then the 16-bit words: both aligned).
-        -> per blob (z words, y words) and (z offsets, y offsets), views of it on the device."""
-        dev = self.m.device
-        offs = [np.concatenate([[0], np.cumsum(hd[k])]).astype(np.int64) for hd in heads for k in ("zl", "yl")]
-        words = [np.frombuffer(b, "<i2", hd["zw"] + hd["yw"], hd["pos"]) for b, hd in zip(blobs, heads)]
-        noff = sum(len(o) for o in offs)
-        host = np.empty(8 * noff + 2 * sum(len(w) for w in words), np.uint8)
-        host[:8 * noff].view(np.int64)[:] = np.concatenate(offs)
-        host[8 * noff:].view(np.int16)[:] = np.concatenate(words)
-        up = torch.from_numpy(host).to(dev)
-        off_d, word_d = up[:8 * noff].view(torch.int64), up[8 * noff:].view(torch.int16)
-        pay, offd = [], []
-        o = wpos = 0
-        for hd in heads:
-            nz, ny = len(hd["zl"]) + 1, len(hd["yl"]) + 1
-            offd.append((off_d[o:o + nz], off_d[o + nz:o + nz + ny]))
-            o += nz + ny
-            pay.append((word_d[wpos:wpos + hd["zw"]], word_d[wpos + hd["zw"]:wpos + hd["zw"] + hd["yw"]]))
-            wpos += hd["zw"] + hd["yw"]
-        return pay, offd
-
-    def _decode_hyper_latents(self, heads, pay, offd, bad, side, main):
-        """The z symbols of every blob, each blob's launch on its own stream of ``side``, joined on ``main``; blob k's
-        bad-stream count goes to bad[2 k]."""
-        dev = self.m.device
-        outs = []
-        for k, (st, hd) in enumerate(zip(side, heads)):
-            if st is not main:
-                st.wait_stream(main)
-            with torch.cuda.stream(st):
-                shape = (hd["n"], hd["hz"], hd["wz"], hd["cz"])
-                outs.append(rans_decode(pay[k][0], hd["zl"], channel_table_ids(shape, dev), shape, self.z_tables, hd["sz"], hd["lz"],
-                                        bad=bad[2 * k:2 * k + 1], offsets=offd[k][0]))
-        for st, out in zip(side, outs):
-            if st is not main:
-                main.wait_stream(st)
-                out.record_stream(main)
-        return outs
-
     def transcode(self, blob: bytes, shift=None, target_bpp=None) -> bytes:
         """``transcode_many`` of one bitstream; ``shift`` / ``target_bpp``: a value or one per image.  ``last_report``: [its rows]."""
         return self.transcode_many([blob], None if shift is None else [shift], None if target_bpp is None else [target_bpp])[0]
@@ -1842,9 +1808,9 @@ class Codec:
         (csrc/quant_step.hip, one rule): y_hat0 = step_value(s0, mu, step[k0]) is what ``decompress`` would feed the
         synthesis, s1 = step_round(step_diff(y_hat0, mu), inv_step[k1]) and t1 = step_table_id(base, k1) are coded.  The output is
         ``compress_latents(z_hat, y_hat0, (H, W))`` on the grid k1, byte for byte: wire format 3, 5 or 7 (``StepGrid.shifted``),
-        the z streams and their header fields copied from the source.  The work is the front of ``decompress_many`` -- z decoded
-        side by side, the hyper-synthesis, y decoded with the source grid's tables, pipelined the same way -- then one
-        requantisation launch and the y coder per blob; no analysis, no synthesis.
+        the z streams and their header fields copied from the source.  The work is ``_decode_front``, which ``decompress_many``
+        drives too -- z decoded side by side, the hyper-synthesis, y decoded with the source grid's tables, pipelined largest
+        first -- then one requantisation launch and the y coder per blob; no analysis, no synthesis.
         Exactly one of ``shift`` / ``target_bpp``, each ONE value for every blob or a sequence with one entry per blob, an entry
         being a value or one per image of that blob (``check_shifts`` / ``check_budgets``).  ``target_bpp``: per image the SMALLEST
         d whose exact coded cost fits target_bpp H W -- ``select_steps`` over d = 0 .. STEP_MAX - min(k0) with the bits
@@ -1876,66 +1842,29 @@ class Codec:
         srcs = [g.indexes(hd["h"], hd["w"]) for g, hd in zip(grids, heads)]
         dev = m.device
         with torch.cuda.device(dev):
-            main = torch.cuda.current_stream()
-            side = self._side_streams(len(blobs)) if len(blobs) > 1 and not torch.cuda.is_current_stream_capturing() else [main] * len(blobs)
-            bad = torch.zeros((2 * len(blobs),), dtype=torch.int32, device=dev)
-            pay, offd = self._upload_streams(blobs, heads)
             lut = cached_step_lut(dev)
-            # every blob's step tensors and source map go up here, before anything is enqueued (a map grid keeps its own copy)
+            # every blob's source map goes up here, before anything is enqueued (a map grid keeps its own copy)
             src_d = [g.on(dev)[0] if g.kind == "map" else torch.from_numpy(s).to(dev) for g, s in zip(grids, srcs)]
-            for grid in grids:
-                grid.on(dev)
-            zis = self._decode_hyper_latents(heads, pay, offd, bad, side, main)
-            # as decompress_many: the blobs pipelined largest first, blob k's latents decoding on its stream while the caller's
-            # stream runs blob k + 1's hyper-synthesis; only the first hyper-synthesis keeps stream-K
-            piped = PIPELINE_BLOBS and len(heads) > 1 and side[0] is not main
-            order = sorted(range(len(heads)), key=lambda k: -(heads[k]["n"] * heads[k]["h"] * heads[k]["w"])) if piped else list(range(len(heads)))
-            hypers, bases, syms = [None] * len(heads), [None] * len(heads), [None] * len(heads)
-            for i, k in enumerate(order):
-                hd, st = heads[k], side[k]
-                with ops.static_schedules(piped and i > 0):
-                    hyper = m._hyper_synthesis(int_to_float(zis[k]))
-                if tuple(hyper.shape) != (hd["n"], hd["h"], hd["w"], 2 * hd["c"]):
-                    raise capi.SntcError(capi.ERR_BAD_SHAPE, f"hyper-synthesis output {tuple(hyper.shape)} does not match the latents "
-                                         f"{(hd['n'], hd['h'], hd['w'], hd['c'])}")
-                hypers[k], bases[k] = hyper, scale_table_ids(hyper)
-                tid = grids[k].table_ids(bases[k])
-                if st is not main:
-                    st.wait_stream(main)
-                with torch.cuda.stream(st):
-                    syms[k] = rans_decode(pay[k][1], hd["yl"], tid, (hd["n"], hd["h"], hd["w"], hd["c"]), self.y_tables, hd["sy"], hd["ly"],
-                                          bad=bad[2 * k + 1:2 * k + 2], offsets=offd[k][1])
-                if st is not main:
-                    tid.record_stream(st)
-            joined = set()
-
-            def join(k):                      # blob k's symbols on the caller's stream, once
-                if side[k] is not main and k not in joined:
-                    main.wait_stream(side[k])
-                    syms[k].record_stream(main)
-                joined.add(k)
-
+            f = self._decode_front(blobs, heads)
+            main, lanes, syms, hypers, bases = f["main"], f["lanes"], f["syms"], f["hypers"], f["bases"]
             if shift is None:
-                for k in order:
-                    join(k)
-                shifts = self._shift_control(heads, zis, syms, hypers, bases, srcs, src_d, budgets, bad)
+                for k in f["order"]:
+                    ops.join(main, lanes[k], made=(syms[k],))
+                shifts = self._shift_control(heads, f["zis"], syms, hypers, bases, srcs, src_d, budgets, f["bad"])
             jobs = [None] * len(heads)
-            for k in order:                   # blob k requantised and coded while the later blobs' latents still decode
+            for k in f["order"]:              # blob k requantised and coded while the later blobs' latents still decode
                 hd = heads[k]
-                join(k)
+                if shift is not None:
+                    ops.join(main, lanes[k], made=(syms[k],))
                 out = grids[k].shifted(shifts[k])
                 dst = torch.from_numpy(np.ascontiguousarray(out.indexes(hd["h"], hd["w"]))).to(dev)
                 sym, tid = ops.step_requant_symbols(syms[k], hypers[k], bases[k], src_d[k], dst, lut)
-                ys, ylen = rans_encode_launch(sym, tid, self.y_tables, hd["sy"], hd["ly"])
-                z_end = hd["pos"] + 2 * hd["zw"]
-                jobs[k] = dict(n=hd["n"], H=hd["H"], W=hd["W"], sz=hd["sz"], sy=hd["sy"], lz=hd["lz"], ly=hd["ly"], zlen=None, zl=hd["zl"],
-                               zbytes=bytes(blobs[k][hd["pos"]:z_end]), dims=tuple(hd[f] for f in ("c", "cz", "hz", "wz", "h", "w")),
-                               ys=ys, ylen=ylen, grid=out)
+                jobs[k] = dict(n=hd["n"], H=hd["H"], W=hd["W"], sz=hd["sz"], sy=hd["sy"], lz=hd["lz"], ly=hd["ly"], grid=out,
+                               dims=tuple(hd[d] for d in ("c", "cz", "hz", "wz", "h", "w")),
+                               copied=(hd["zl"], np.frombuffer(blobs[k], "<i2", hd["zw"], hd["pos"])),
+                               groups=[rans_encode_launch(sym, tid, self.y_tables, hd["sy"], hd["ly"])])
             out = self._finish(jobs)
-            nbad = int(bad.sum().item())
-            if nbad:
-                total = sum(hd["n"] * (hd["sz"] + hd["sy"]) for hd in heads)
-                raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {total} rANS streams did not terminate cleanly")
+            _raise_if_bad(int(f["bad"].sum().item()), sum(hd["n"] * (hd["sz"] + hd["sy"]) for hd in heads))
             return out
 
     def _shift_control(self, heads, zis, syms, hypers, bases, srcs, src_d, budgets, bad):
@@ -1951,10 +1880,7 @@ class Codec:
             cost_y = step_requant_ladder_cost(syms[k], hypers[k], bases[k], src_d[k], cands[k], self.y_tables)
             parts += [cost_z, cost_y.reshape(-1)]
         host = torch.cat(parts).cpu().numpy()                                                                    # the one read-back
-        nbad = int(host[:len(bad)].sum())
-        if nbad:
-            total = sum(hd["n"] * (hd["sz"] + hd["sy"]) for hd in heads)
-            raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {total} rANS streams did not terminate cleanly")
+        _raise_if_bad(int(host[:len(bad)].sum()), sum(hd["n"] * (hd["sz"] + hd["sy"]) for hd in heads))
         self.last_report, shifts, o = [], [], len(bad)
         for k, hd in enumerate(heads):
             n, S = hd["n"], len(cands[k])
@@ -1969,9 +1895,6 @@ class Codec:
             self.last_report.append(report)
             shifts.append([r["step_chosen"] for r in report])
         return shifts
-
-    def _side_streams(self, count):
-        return ops.side_streams(count, self.m.device)
 
 
 # -- wire format v4: pure host functions (numbers in, numbers out; no device) ---------------------------------------------
@@ -2070,27 +1993,25 @@ class FactorizedCodec:
             scratch, lens, _ = rans_encode_channels_launch(y, self.y_tables, segments, lanes)
         else:
             scratch, lens = rans_encode_launch(round_to_int(y), channel_table_ids(y.shape, y.device), self.y_tables, segments, lanes)
-        return dict(n=n, H=H, W=W, y=y, segments=segments, lanes=lanes, scratch=scratch, lens=lens)
+        return dict(n=n, H=H, W=W, dims=tuple(y.shape[1:]), segments=segments, lanes=lanes, groups=[(scratch, lens)])
 
     def _launch(self, x):
         """analysis -> ``_launch_latents``."""
         return self._launch_latents(self.m.infer_latent_rvs(x).uq[0].loc, x.shape[1:3])
 
-    def _blob(self, j, lens_h, words):
-        _, h, w, c = j["y"].shape
-        return pack_v4(ARITH[self.m._precision], j["n"], j["H"], j["W"], c, h, w, j["segments"], j["lanes"], lens_h) + words.tobytes()
-
-    def _finish_one(self, j):
-        lens_h = j["lens"].cpu().numpy().astype(np.int64)
-        words = rans_encode_finish(j["scratch"], j["lens"], lens_h).cpu().numpy()
-        ops.check_conv_status()       # the copies synchronised the stream: a flagged stream-K launch raises here, not a wrong file
-        return self._blob(j, lens_h, words)
+    def _finish(self, jobs):
+        """Launched jobs -> their blobs (``finish_streams``: two read-backs for all of them)."""
+        out = []
+        for j, ((lens_h, words),) in zip(jobs, finish_streams([j["groups"] for j in jobs])):
+            h, w, c = j["dims"]
+            out.append(pack_v4(ARITH[self.m._precision], j["n"], j["H"], j["W"], c, h, w, j["segments"], j["lanes"], lens_h) + words.tobytes())
+        return out
 
     def compress_latents(self, y_loc, image_hw) -> bytes:
         """Latents of this model for images of ``image_hw`` = (H, W) -- the analysis', or ones refined by iterative inference --
         -> the bitstream ``decompress`` reads.  ``compress(x)`` is this on ``infer_latent_rvs(x)``."""
         with torch.cuda.device(self.m.device):
-            return self._finish_one(self._launch_latents(y_loc.contiguous(), image_hw))
+            return self._finish([self._launch_latents(y_loc.contiguous(), image_hw)])[0]
 
     def latents_cost(self, y_loc, x):
         """``Codec.latents_cost`` for the one latent: -> (None, cost_y int64 [n] in 2^-16 bit, uint8 pixels, integer SSE [n])."""
@@ -2104,45 +2025,13 @@ class FactorizedCodec:
         m = self.m
         x = m._as_device_images(x)
         with torch.cuda.device(m.device):
-            return self._finish_one(self._launch(x))
+            return self._finish([self._launch(x)])[0]
 
     def compress_many(self, xs):
         """``compress`` for several batches -> their bitstreams, in order, byte for byte what one ``compress`` per batch returns.
         The batches' analyses and coder launches run side by side on the library's side streams; the stream lengths of ALL
         batches come back in one copy, the packed payloads in another (``Codec.compress_many``)."""
-        m = self.m
-        xs = [m._as_device_images(x) for x in xs]
-        if not xs:
-            return []
-        with torch.cuda.device(m.device):
-            main = torch.cuda.current_stream()
-            side = ops.side_streams(len(xs), m.device) if len(xs) > 1 and not torch.cuda.is_current_stream_capturing() else [main] * len(xs)
-            jobs = []
-            for st, x in zip(side, xs):
-                if st is not main:
-                    st.wait_stream(main)
-                with torch.cuda.stream(st):
-                    jobs.append(dict(self._launch(x), st=st))
-            for j in jobs:
-                if j["st"] is not main:
-                    main.wait_stream(j["st"])
-                    for t in (j["scratch"], j["lens"]):
-                        t.record_stream(main)
-            lens_h = torch.cat([j["lens"] for j in jobs]).cpu().numpy().astype(np.int64)                             # read-back 1 of 2
-            pays, o = [], 0
-            for j in jobs:
-                ns = j["lens"].numel()
-                j["lens_h"] = lens_h[o:o + ns]
-                o += ns
-                pays.append(rans_encode_finish(j["scratch"], j["lens"], j["lens_h"]))
-            words = torch.cat(pays).cpu().numpy()                                                                    # read-back 2 of 2
-            ops.check_conv_status()
-        out, o = [], 0
-        for j in jobs:
-            nw = int(j["lens_h"].sum())
-            out.append(self._blob(j, j["lens_h"], words[o:o + nw]))
-            o += nw
-        return out
+        return _compress_many(self, xs)
 
     def _parse(self, blob: bytes):
         """Header and stream lengths of one blob, checked against THIS model: nothing later trusts the header."""
@@ -2164,43 +2053,23 @@ class FactorizedCodec:
         heads = [self._parse(b) for b in blobs]
         dev = m.device
         with torch.cuda.device(dev):
-            main = torch.cuda.current_stream()
-            side = ops.side_streams(len(blobs), dev) if len(blobs) > 1 and not torch.cuda.is_current_stream_capturing() else [main] * len(blobs)
+            main, lanes = ops.lanes(len(blobs), dev)
             bad = torch.zeros((len(blobs),), dtype=torch.int32, device=dev)
-            # ONE upload (int64 offsets first, then the 16-bit words: both aligned)
-            offs = [np.concatenate([[0], np.cumsum(hd["lens"])]).astype(np.int64) for hd in heads]
-            words = [np.frombuffer(b, "<i2", hd["words"], hd["pos"]) for b, hd in zip(blobs, heads)]
-            noff = sum(len(o) for o in offs)
-            host = np.empty(8 * noff + 2 * sum(len(w) for w in words), np.uint8)
-            host[:8 * noff].view(np.int64)[:] = np.concatenate(offs)
-            host[8 * noff:].view(np.int16)[:] = np.concatenate(words)
-            up = torch.from_numpy(host).to(dev)
-            off_d, word_d = up[:8 * noff].view(torch.int64), up[8 * noff:].view(torch.int16)
-            y_hats, o, wpos = [], 0, 0
-            for k, (hd, st) in enumerate(zip(heads, side)):
-                if st is not main:
-                    st.wait_stream(main)
-                with torch.cuda.stream(st):
-                    y_hats.append(rans_decode_channels(word_d[wpos:wpos + hd["words"]], hd["lens"], (hd["n"], hd["h"], hd["w"], hd["c"]),
-                                                       self.y_tables, hd["segments"], hd["lanes"], bad=bad[k:k + 1],
-                                                       offsets=off_d[o:o + len(offs[k])]))
-                if st is not main:
-                    up.record_stream(st)
-                o += len(offs[k])
-                wpos += hd["words"]
-            beside = side[0] is not main
+            up, views = pack_upload([np.concatenate([[0], np.cumsum(hd["lens"])]).astype(np.int64) for hd in heads] +
+                                    [np.frombuffer(b, "<i2", hd["words"], hd["pos"]) for b, hd in zip(blobs, heads)], dev)
+            y_hats = []
+            for k, (hd, st) in enumerate(zip(heads, lanes)):
+                with ops.fork(main, st, reads=(up, bad)):
+                    y_hats.append(rans_decode_channels(views[len(heads) + k], hd["lens"], (hd["n"], hd["h"], hd["w"], hd["c"]), self.y_tables,
+                                                       hd["segments"], hd["lanes"], bad=bad[k:k + 1], offsets=views[k]))
+            beside = len(set(lanes)) > 1                           # the blobs have streams of their own
             order = sorted(range(len(heads)), key=lambda k: -(heads[k]["n"] * heads[k]["h"] * heads[k]["w"]))
             out = [None] * len(heads)
             for i, k in enumerate(order):
-                hd, st = heads[k], side[k]
-                if st is not main:
-                    main.wait_stream(st)
-                    y_hats[k].record_stream(main)
+                hd = heads[k]
+                ops.join(main, lanes[k], made=(y_hats[k],))
                 with ops.static_schedules(beside and i + 1 < len(order)):
                     out[k] = m.decode(y_hats[k], None, (hd["H"], hd["W"]), check=False)
-            nbad = int(bad.sum().item())                           # synchronises the stream
-            if nbad:
-                total = sum(hd["n"] * hd["segments"] for hd in heads)
-                raise capi.SntcError(capi.ERR_BAD_SHAPE, f"bitstream corrupt: {nbad} of {total} rANS streams did not terminate cleanly")
+            _raise_if_bad(int(bad.sum().item()), sum(hd["n"] * hd["segments"] for hd in heads))     # synchronises the stream
             ops.check_conv_status()       # wrong pixels never leave without an error
             return out

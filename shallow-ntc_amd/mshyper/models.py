@@ -636,34 +636,25 @@ class Model:
         if len(codes) < 2 or len(codes) > 4 or not hasattr(syn, "hidden_many") or self._synthesis.takes_s3(*codes[0][1].shape[1:3]):
             return [self.decode(z, s, hw, reference=r, check=check) for z, s, hw, r in codes]
         with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream()
-            self._set_streams = ops.side_streams(len(codes), self.device)
+            cur, lanes = ops.lanes(len(codes), self.device)
             y_hats = []
-            for st, (z_hat, sym, _hw, _r) in zip(self._set_streams, codes):
-                st.wait_stream(cur)
-                with torch.cuda.stream(st):
-                    y_hat = ops.dequant_scale_normal(sym, self._hyper_synthesis.leading_channels(z_hat, sym.shape[-1]))
-                y_hat.record_stream(cur)
-                y_hats.append(y_hat)
-            for st in self._set_streams[:len(codes)]:
-                cur.wait_stream(st)
+            for st, (z_hat, sym, _hw, _r) in zip(lanes, codes):
+                with ops.fork(cur, st):
+                    y_hats.append(ops.dequant_scale_normal(sym, self._hyper_synthesis.leading_channels(z_hat, sym.shape[-1])))
+            for st, y_hat in zip(lanes, y_hats):
+                ops.join(cur, st, made=(y_hat,))
             hidden = syn.hidden_many(y_hats)
             outs = []
             if hidden is None:
                 for y_hat, (_z, _s, hw, ref) in zip(y_hats, codes):
                     outs.append(self._pixels(y_hat, hw, ref))
             else:
-                for st, hid, (_z, _s, hw, ref) in zip(self._set_streams, hidden, codes):
-                    st.wait_stream(cur)
-                    with torch.cuda.stream(st):
+                for st, hid, (_z, _s, hw, ref) in zip(lanes, hidden, codes):
+                    with ops.fork(cur, st, reads=(hid,)):
                         px, sse = syn.pixels_from_hidden(hid, hw[0], hw[1], ref)
-                    hid.record_stream(st)
-                    px.record_stream(cur)
-                    if sse is not None:
-                        sse.record_stream(cur)
                     outs.append(px if ref is None else (px, sse))
-                for st in self._set_streams[:len(codes)]:
-                    cur.wait_stream(st)
+                for st, out in zip(lanes, outs):
+                    ops.join(cur, st, made=out if isinstance(out, tuple) else (out,))
             if check:
                 ops.check_conv_status()
             return outs

@@ -6,6 +6,7 @@ allocator.  No torch compute op is used on the hot path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -53,7 +54,9 @@ def side_streams(n, device=None):
     for that stream's, and an event recorded behind them waits as well (``tools/microbench/hw_queues.py`` prints the map; with
     every component creating streams of its own, the pipelined ``decompress_many`` ran 6.35 ms in ``bench.py``'s process and
     5.37 ms in a process with three streams).  The pool's first three streams are created together, on first use; asking for more
-    than three works and shares queues (raising ``GPU_MAX_HW_QUEUES`` instead costs the two-stream decode 5 %)."""
+    than three works and shares queues (raising ``GPU_MAX_HW_QUEUES`` instead costs the two-stream decode 5 %).
+    The codecs do not wait on or record for these streams themselves: ``lanes`` hands them out, ``fork`` / ``join`` below are
+    the one copy of the rule for work that leaves the caller's stream and comes back."""
     if device is None:
         device = torch.cuda.current_device()
     idx = device.index if isinstance(device, torch.device) else int(device)
@@ -63,6 +66,42 @@ def side_streams(n, device=None):
     while len(pool) < max(int(n), SIDE_POOL_MIN):
         pool.append(torch.cuda.Stream(device=idx))
     return pool[:int(n)]
+
+
+def lanes(count, device=None, alone=False):
+    """-> (main, lanes): the caller's current stream and ``count`` streams for ``fork``: the pool's (``side_streams``), or main
+    itself ``count`` times while it is capturing or when there is nothing to run side by side (``count`` < 2; ``alone``: a single
+    job takes a pooled stream too)."""
+    main = torch.cuda.current_stream(device)
+    if torch.cuda.is_current_stream_capturing() or count < (1 if alone else 2):
+        return main, [main] * count
+    return main, side_streams(count, device)
+
+
+@contextlib.contextmanager
+def fork(main, lane, reads=()):
+    """Run the body on ``lane``, behind everything ``main`` holds so far.  ``reads``: the tensors allocated on ``main`` that the
+    body reads or writes; they are recorded on the lane, so the caching allocator does not hand their memory to later work on
+    ``main`` while the lane still uses it -- also when the caller drops them early, on an error path.  With ``lane is main`` only
+    the body runs."""
+    if lane is main:
+        yield
+        return
+    lane.wait_stream(main)
+    with torch.cuda.stream(lane):
+        yield
+    for t in reads:
+        t.record_stream(lane)
+
+
+def join(main, lane, made=()):
+    """``main`` waits for what ``lane`` holds so far; ``made``: the tensors allocated on the lane (inside ``fork``) that ``main``
+    goes on to use, recorded there.  Nothing with ``lane is main``."""
+    if lane is main:
+        return
+    main.wait_stream(lane)
+    for t in made:
+        t.record_stream(main)
 
 
 _COMPANIONS = {}
