@@ -55,6 +55,23 @@ __device__ __forceinline__ bool first_of_desc(F&& f) {
   }
 }
 
+// f(integral_constant<int, 0>), ..., f(N - 1), every one
+template <int N, int I = 0, class F>
+__device__ __forceinline__ void each_of(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    each_of<N, I + 1>(f);
+  }
+}
+
+// a step's WR / LD / PF switch: an integral_constant (the steady state and the old tails: no branch) or a run-time bool
+template <class T> constexpr bool gg_yes = std::is_same_v<T, std::integral_constant<bool, true>>;
+template <class T>
+__device__ __forceinline__ constexpr bool gg_flag(T f) {
+  if constexpr (std::is_same_v<T, bool>) return f;
+  else return T::value;
+}
+
 __device__ __forceinline__ f32x4 buf_load(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
   const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)soff, 0);
   return __builtin_bit_cast(f32x4, v);
@@ -107,6 +124,12 @@ __device__ __forceinline__ float apply_epilogue1(float v, int epi, const float* 
 // workgroups per CU the register budget must allow (= waves per SIMD for 256-thread workgroups): what the LDS ring admits
 constexpr int gg_waves(int tiles) { return tiles == 1 ? 4 : (tiles <= 3 ? 3 : 2); }
 
+// instances of the register-staged vector pipeline whose K loop runs with compile-time ring slots (SLOTS3 in gg_kernel; the
+// library-wide switch is kGGRingSlots, sntc_internal.h).  An instance is listed only if the loop keeps its waves per SIMD and adds
+// no spill (tools/kernel_resources.py): every shape but 256 x 128, which sits at 255 registers with the old loop
+// and spills two with the new one
+constexpr bool gg_const_slots(int TM, int TN) { return !(TM == 2 && TN == 4); }
+
 // BF3 (experiment, DESIGN.md 8: "bf16 x 3"): every fp32 operand is split into three bfloat16 terms hi + mid + lo (24
 // mantissa bits together) and the product is accumulated in fp32 from the six significant cross terms on
 // v_mfma_f32_32x32x16_bf16 -- 6 MFMAs of 32 cycles for K = 16 against 8 fp32 MFMAs of 64 cycles.  The weights are split
@@ -156,8 +179,28 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
   // 128 x 128 one with its column-major twin; 128 x 96 sits at 163 of 168 registers, the 1 x 4-tile 128 x 128 instance spills
   // 71 registers with a second set and the wider tiles have no room: they keep the single set either way
   constexpr bool TWO = kGGTwoSets && VEC && DBUF && !DMA && !FUSE2 && (TM * TN <= 2 || (TM == 2 && TN == 2));
+  // SLOTS3: the single-set loop runs three stages per iteration with the ring slots 0, 1, 2 as compile-time constants (every piece
+  // starts at slot 0, so stage j of a piece sits in slot j % 3): the LDS addresses of write_lds / read_frag are a loop-invariant
+  // lane register plus an immediate instead of slot * SLOT + lane offset re-made every stage, and the rotation of three slot
+  // registers goes.  Per instance (gg_const_slots): only where the register count holds the instance's waves per SIMD without a spill
+  // (the prologue instances keep the old loop as well: with abs / square between the staging registers and LDS the compiler
+  // rejects the walk's scalar pin in advance_stage)
+  constexpr bool SLOTS3 = kGGRingSlots && VEC && !PRO && !BF3 && !DMA && !TWO && gg_const_slots(TM, TN);
   constexpr bool RBUF = TWO || (DBUF && TM * TN <= 3 && !FUSE2);   // second staging register set for a tile's first two stages
   static_assert(RING * SLOT >= 4 * EPW + (DMA ? SLOT : 0), "epilogue staging (and one prefetched stage) must fit in the stage ring");
+  if constexpr (SLOTS3 && !COLM) {
+    // register floor: the loop needs a few registers fewer than the old one, which takes 128 x 64 (129 -> 127) and the strip-major
+    // 128 x 128 (169 -> 166) under an occupancy edge: the hardware could then hold one workgroup more of them on a CU than the
+    // instance's __launch_bounds__ and the schedules measured with it count on.  With the worker counts held where they were,
+    // that build ran the two-stream step 1.3 % slower, the 18-image HS2 stream-K launch 500 or 630 us from step to step
+    // (DESIGN.md 8).  Naming the first register past the edge of W + 1 waves per SIMD (512 registers, allocated in eights)
+    // keeps the allocation at the launch bound's W.  The column-major twin has none: it is the one instance that runs above
+    // its launch bound on purpose (three per CU at 166 <= 168 registers)
+    constexpr int W = FUSE2 ? 2 : gg_waves(TM * TN);
+    if constexpr (W == 2) asm volatile("" ::: "v168");        // 169 registers -> 176 allocated: two waves
+    else if constexpr (W == 3) asm volatile("" ::: "v128");   // 129 -> 136: three
+    else asm volatile("" ::: "v96");                          // 97 -> 104: four
+  }
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* ring = reinterpret_cast<float*>(smem);                  // [RING][BM + BN][16]
   int4* rinfo_all = reinterpret_cast<int4*>(ring + RING * SLOT); // [2][BM] (n, qy, qx, valid) of the current / next tile
@@ -316,6 +359,13 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
       if constexpr (kGGTapState) {          // scalar: the delta walks the tap grid with adds, and starts over at the slab's end
         ld_delta = tap_end ? 0u : ld_delta + (row_end ? tap_drow : tap_dx);
         ld_sel = gg_tap_select(ld_ty, ld_tx);
+      }
+      if constexpr (SLOTS3) {
+        // the walk's state stays in scalar registers from one step to the next: with three steps in one loop body the compiler
+        // otherwise merges their tap_end chains, carries the flags in vector registers (ld_cc += tap_end becomes v_addc_co), and
+        // every buffer load gets a waterfall loop for its now "divergent" scalar offset
+        asm volatile("" : "+s"(ld_cc), "+s"(ld_t), "+s"(ld_ty), "+s"(ld_tx));
+        if constexpr (kGGTapState) asm volatile("" : "+s"(ld_delta), "+s"(ld_sel));
       }
       set_tap(ld_ty, ld_tx);
     }
@@ -608,7 +658,7 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
       dma_issued = 0;
     } else {
     // ---- prologue: stages k0, k0+1 -> ring slots 0, 1; stage k0+2 in flight
-    int s_cur = 0, s_n1 = 1, s_n2 = 2;
+    int r_cur = 0, r_n1 = 1, r_n2 = 2;
     if (n > 0) write_lds(R0, 0);
     if (RBUF) {
       if (n > 1) write_lds(R1, 1);
@@ -625,9 +675,12 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
     // PF: the first fragments of stage j+1 are prefetched.  The steady-state steps have all three and no branch.
     // R: the staging set of the step (single set: always R0; TWO: the set of the step's parity, stage j+2 loaded during step
     // j-2, stage j+4 issued now)
-    auto step = [&](Regs& R, auto WR, auto LD, auto PF) {
-      if (decltype(WR)::value && !SNTC_DBG(a, 2)) write_lds(R, s_n2);         // stage j+2, loaded during step j-1 (TWO: j-2)
-      if (decltype(LD)::value && !SNTC_DBG(a, 1)) load_regs(R);               // stage j+3 (TWO: j+4)
+    // S: the ring slot of stage j as a compile-time constant (SLOTS3), or -1: the slots are the rotating s_cur / s_n1 / s_n2
+    auto step = [&](Regs& R, auto WR, auto LD, auto PF, auto S) {
+      constexpr int kS = decltype(S)::value;
+      const int s_cur = kS < 0 ? r_cur : kS, s_n1 = kS < 0 ? r_n1 : (kS + 1) % 3, s_n2 = kS < 0 ? r_n2 : (kS + 2) % 3;
+      if (gg_flag(WR) && !SNTC_DBG(a, 2)) write_lds(R, s_n2);                 // stage j+2, loaded during step j-1 (TWO: j-2)
+      if (gg_flag(LD) && !SNTC_DBG(a, 1)) load_regs(R);                       // stage j+3 (TWO: j+4)
       if (BF3) {
         Frag3 F3;
         read_frag3(F3, s_cur);
@@ -635,7 +688,7 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
       } else if (DBUF) {
         if (!SNTC_DBG(a, 8)) read_frag(F1, s_cur, 1);
         mfma_group(F0);
-        if (decltype(PF)::value && !SNTC_DBG(a, 8)) read_frag(F0, s_n1, 0);   // under this stage's remaining MFMAs
+        if (gg_flag(PF) && !SNTC_DBG(a, 8)) read_frag(F0, s_n1, 0);           // under this stage's remaining MFMAs
         mfma_group(F1);
       } else {
         read_frag(F0, s_cur, 0);
@@ -643,7 +696,7 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
         read_frag(F0, s_cur, 1);
         mfma_group(F0);
       }
-      if (DBUF && VEC && decltype(WR)::value && decltype(LD)::value && decltype(PF)::value) {
+      if constexpr (DBUF && VEC && gg_yes<decltype(WR)> && gg_yes<decltype(LD)> && gg_yes<decltype(PF)>) {
         // steady state: order the step's memory instructions BETWEEN its MFMAs (mask 0x8 MFMA, 0x200 DS write, 0x20 VMEM
         // read, 0x100 DS read): an MFMA occupies the pipe for 64 cycles but its issue slot for a few, so everything
         // placed behind the first one is free; the fragment reads get a full MFMA group to land before they are used
@@ -662,41 +715,59 @@ __global__ void __launch_bounds__(256, FUSE2 ? 2 : gg_waves(TM * TN)) gg_kernel(
       __builtin_amdgcn_sched_barrier(0);                   // every MFMA of the step is issued before the wave waits
       if (!SNTC_DBG(a, 4)) __syncthreads();
       __builtin_amdgcn_sched_barrier(0);
-      const int t = s_cur; s_cur = s_n1; s_n1 = s_n2; s_n2 = t;
+      if constexpr (kS < 0) { r_cur = s_n1; r_n1 = s_n2; r_n2 = s_cur; }
     };
     using Yes = std::integral_constant<bool, true>;
     using No = std::integral_constant<bool, false>;
+    using Rot = std::integral_constant<int, -1>;
     if constexpr (TWO) {
       // steady state: two steps per iteration, R0 on the even and R1 on the odd stages of the piece, no register copies.  ONE
       // exit, after a whole pair (a second exit between the two steps made the compiler carry the accumulators out of the loop
       // in a second register set: 16 to 32 v_mov_b64 per iteration); a fifth remaining step is the pair's first half again
       int j = 0;
       for (; j + 5 < n; j += 2) {
-        step(R0, Yes{}, Yes{}, Yes{});
-        step(R1, Yes{}, Yes{}, Yes{});
+        step(R0, Yes{}, Yes{}, Yes{}, Rot{});
+        step(R1, Yes{}, Yes{}, Yes{}, Rot{});
       }
       int rem = n - j;                         // 0 .. 5
       bool odd = false;
       if (rem == 5) {
-        step(R0, Yes{}, Yes{}, Yes{});
+        step(R0, Yes{}, Yes{}, Yes{}, Rot{});
         odd = true;
         rem = 4;
       }
       // tail: up to two stages wait in the sets (stage j+2 in the set of j's parity, then stage j+3 in the other)
       if (rem >= 4) {
-        if (odd) step(R1, Yes{}, No{}, Yes{}); else step(R0, Yes{}, No{}, Yes{});
+        if (odd) step(R1, Yes{}, No{}, Yes{}, Rot{}); else step(R0, Yes{}, No{}, Yes{}, Rot{});
         odd = !odd;
       }
       if (rem >= 3) {
-        if (odd) step(R1, Yes{}, No{}, Yes{}); else step(R0, Yes{}, No{}, Yes{});
+        if (odd) step(R1, Yes{}, No{}, Yes{}, Rot{}); else step(R0, Yes{}, No{}, Yes{}, Rot{});
       }
-      if (rem >= 2) step(R0, No{}, No{}, Yes{});
-      if (rem >= 1) step(R0, No{}, No{}, No{});
+      if (rem >= 2) step(R0, No{}, No{}, Yes{}, Rot{});
+      if (rem >= 1) step(R0, No{}, No{}, No{}, Rot{});
+    } else if constexpr (SLOTS3) {
+      // steady state: three steps per iteration, stage j in slot j % 3.  ONE exit, after a whole triple (see TWO above).  The
+      // 0 .. 5 steps left: one copy per POSITION (its slot a constant), what the step still writes, loads and prefetches a
+      // run-time flag of the steps left.  One straight line per remainder was tried first: the compiler then keeps the
+      // accumulators in two register sets across the five-way branch (+32 registers on 128 x 64, +64 on 128 x 128)
+      int j = 0;
+#pragma unroll 1
+      for (; j + 5 < n; j += 3) {
+        step(R0, Yes{}, Yes{}, Yes{}, std::integral_constant<int, 0>{});
+        step(R0, Yes{}, Yes{}, Yes{}, std::integral_constant<int, 1>{});
+        step(R0, Yes{}, Yes{}, Yes{}, std::integral_constant<int, 2>{});
+      }
+      const int rem = n - j;
+      each_of<5>([&](auto Pc) {
+        const int left = rem - decltype(Pc)::value;                            // steps left, this one included
+        if (left > 0) step(R0, left >= 3, left > 3, left >= 2, std::integral_constant<int, decltype(Pc)::value % 3>{});
+      });
     } else {
-      for (int j = 0; j + 3 < n; ++j) step(R0, Yes{}, Yes{}, Yes{});
-      if (n >= 3) step(R0, Yes{}, No{}, Yes{});
-      if (n >= 2) step(R0, No{}, No{}, Yes{});
-      if (n >= 1) step(R0, No{}, No{}, No{});
+      for (int j = 0; j + 3 < n; ++j) step(R0, Yes{}, Yes{}, Yes{}, Rot{});
+      if (n >= 3) step(R0, Yes{}, No{}, Yes{}, Rot{});
+      if (n >= 2) step(R0, No{}, No{}, Yes{}, Rot{});
+      if (n >= 1) step(R0, No{}, No{}, No{}, Rot{});
     }
     }   // register-staged pipeline
 

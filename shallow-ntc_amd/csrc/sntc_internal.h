@@ -110,9 +110,15 @@ constexpr int kStage = 16;         // K depth of one pipeline stage
 //   kGGTwoSets   two staging register sets in the steady state: global loads issued two stages ahead of their LDS write: OFF --
 //                measured SLOWER than the single set (the same HS3 launch 615 -> 651 us alone, 594 -> 626 us on top of the tap
 //                state; the step 2.426 -> 2.570 / 2.521 ms), same bits; kept as a switch for the next look at the loads' lead
+//   kGGRingSlots ring slots of the register-staged loop as compile-time constants, three stages per loop iteration: LDS addresses
+//                become immediates.  Per instance through gg_const_slots (gather_gemm_kernel.h); DESIGN.md 8 has the figures
 #ifndef SNTC_GG_TAP_STATE
 #define SNTC_GG_TAP_STATE 1
 #endif
+#ifndef SNTC_GG_RING_SLOTS
+#define SNTC_GG_RING_SLOTS 1
+#endif
+constexpr bool kGGRingSlots = SNTC_GG_RING_SLOTS != 0;
 #ifndef SNTC_GG_TWO_SETS
 #define SNTC_GG_TWO_SETS 0
 #endif
