@@ -72,7 +72,9 @@ enum {                       /* epilogue, v = act(conv + bias) */
   SNTC_EPI_RES_DIV_SQRT = 5, /* y = res / sqrt(v)          (classic tfc.GDN)                    */
   SNTC_EPI_RES_MUL_SQRT = 6, /* y = res * sqrt(v)          (classic inverse tfc.GDN)            */
   SNTC_EPI_MASK_RELU = 7,    /* y = res > 0 ? v : 0        (relu backward; res = forward output) */
-  SNTC_EPI_MASK_LEAKY = 8    /* y = res >= 0 ? v : 0.2 v   (leaky-relu backward)                 */
+  SNTC_EPI_MASK_LEAKY = 8,   /* y = res >= 0 ? v : 0.2 v   (leaky-relu backward)                 */
+  SNTC_EPI_DEQUANT = 9       /* y = v + (float)s, s int32  (decoder: y_hat = symbols + mu, mshyper/models.py:278-279).  A per-call
+                              * override of a SNTC_EPI_STORE plan (sntc_conv_forward_columns_dequant), never a plan's own epilogue */
 };
 
 typedef struct sntc_conv_desc {
@@ -358,6 +360,14 @@ int sntc_conv_plan_drop_choice(sntc_conv_plan* plan, int n, int h, int w, int nc
 int sntc_conv_columns_supported(const sntc_conv_plan* plan, int ncols);
 int sntc_conv_forward_columns(const sntc_conv_plan* plan, const float* x, int n, int h, int w, float* y, const float* res,
                               const float* aux, void* workspace, size_t workspace_bytes, void* stream, int ncols);
+/* The column-limited launch with the decoder's dequantisation in its epilogue: y_hat = v + (float)symbols, where v is what
+ * sntc_conv_forward_columns stores and `symbols` is int32 [n, ho, wo, ncols], indexed as the output -- the bits of
+ * sntc_dequant_mean(symbols, sntc_conv_forward_columns(...)) without the mu round trip and the second launch.  The plan stays a
+ * SNTC_EPI_STORE plan (the encoder's launches of the same plan store plainly); the schedule -- measured or from the cost model --
+ * and the workspace are those of the plain column launch at the same (n, h, w, ncols).  Refuses what sntc_conv_forward_columns
+ * refuses, and a `symbols` pointer that is null or not 16-byte aligned (SNTC_ERR_UNSUPPORTED, nothing launched). */
+int sntc_conv_forward_columns_dequant(const sntc_conv_plan* plan, const float* x, int n, int h, int w, int ncols,
+                                      const int32_t* symbols, float* y_hat, void* workspace, size_t workspace_bytes, void* stream);
 int64_t sntc_conv_columns_flops(const sntc_conv_plan* plan, int n, int h, int w, int ncols);
 int64_t sntc_conv_columns_workspace_bytes(const sntc_conv_plan* plan, int n, int h, int w, int ncols);
 /* variant / nblocks as sntc_conv_launch_info, column_major as sntc_conv_launch_order; any of the three may be NULL */

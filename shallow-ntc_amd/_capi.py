@@ -112,6 +112,7 @@ SIGNATURES = {
     "sntc_conv_plan_drop_choice": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sntc_conv_columns_supported": (C.c_int, [_P, C.c_int]),
     "sntc_conv_forward_columns": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_size_t, _P, C.c_int]),
+    "sntc_conv_forward_columns_dequant": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "sntc_conv_columns_flops": (C.c_int64, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sntc_conv_columns_workspace_bytes": (C.c_int64, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sntc_conv_columns_launch_info": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),

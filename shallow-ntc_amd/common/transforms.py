@@ -145,16 +145,39 @@ class Transform:
         layer (ops.ConvPlan.columns: the same bits as ``self(x)[..., :ncols]``) -- or ``self(x)`` whole where that layer cannot
         run one (several phase groups, split precision, another kernel) or ``ops.MEAN_ONLY_HYPER`` is off: look at the
         result's channel count.  The decoder's hyper-synthesis: y_hat = symbols + mu never reads the raw-sigma half."""
+        tail = self._column_tail(x, ncols)
+        if tail is None:
+            return self(x)
+        head, plan = tail
+        for l in head:
+            x = l(x)
+        return plan.columns(ncols)(x)
+
+    def dequantised(self, x, symbols):
+        """y_hat = symbols + (the transform's first ``symbols.shape[-1]`` output channels): where ``leading_channels`` would run
+        the column-limited launch, that launch adds the int32 symbols in its epilogue and mu is never stored
+        (ops.ConvPlan.columns(...)(x, symbols=...), ``ops.FUSE_DEQUANT``); everywhere else
+        ``ops.dequant_scale_normal(symbols, self.leading_channels(...))``.  The same bits either way."""
+        ncols = symbols.shape[-1]
+        tail = self._column_tail(x, ncols) if ops.FUSE_DEQUANT and symbols.dtype == torch.int32 and symbols.is_contiguous() else None
+        if tail is None:
+            return ops.dequant_scale_normal(symbols, self.leading_channels(x, ncols))
+        head, plan = tail
+        for l in head:
+            x = l(x)
+        return plan.columns(ncols)(x, symbols=symbols)
+
+    def _column_tail(self, x, ncols):
+        """(the layers before the last, the last layer's plan) where that plan can run a column-limited launch of ``ncols`` columns
+        and ``ops.MEAN_ONLY_HYPER`` is on; None otherwise.  Builds the transform on ``x``'s device first."""
         if self._built_on != x.device:
             self.build(x.shape[-1], x.device)
         layers = self._graph.layers if isinstance(self._graph, Seq) else None
         plan = getattr(layers[-1], "plan", None) if layers else None
         if (not ops.MEAN_ONLY_HYPER or type(self)._forward is not Transform._forward or type(plan) is not ops.ConvPlan
                 or not plan.columns_supported(ncols)):
-            return self(x)
-        for l in layers[:-1]:
-            x = l(x)
-        return plan.columns(ncols)(x)
+            return None
+        return layers[:-1], plan
 
     def out_channels(self, input_channels=None):
         return self._graph.shapes(input_channels or self._cin)[1]

@@ -858,7 +858,7 @@ extern "C" int sntc_conv_launch_info(const sntc_conv_plan* p, int n, int h, int 
 // One launch of plan p; with p2 (validated by sntc_conv_forward_fused) the 1x1 plan p2 runs behind p inside the same launch.
 static int conv_forward_impl(const sntc_conv_plan* p, const sntc_conv_plan* p2, const float* x, int n, int h, int w, float* y,
                              const float* res, const float* aux, void* workspace, size_t workspace_bytes, void* stream,
-                             const TuneChoice* force = nullptr, int ncols = 0) {
+                             const TuneChoice* force = nullptr, int ncols = 0, const int32_t* symbols = nullptr) {
   if (!p || !x || !y) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_forward: null argument");
   if (ncols != 0) {      // column-limited launch: refused here, before anything is scheduled or launched
     if (const char* why = columns_error(p, ncols)) return fail(SNTC_ERR_UNSUPPORTED, why);
@@ -866,7 +866,10 @@ static int conv_forward_impl(const sntc_conv_plan* p, const sntc_conv_plan* p2, 
   }
   if (n < 1) return fail(SNTC_ERR_BAD_SHAPE, "sntc_conv_forward: empty batch");
   const sntc_conv_desc& d = p->d;
-  const int epilogue = p2 ? p2->d.epilogue : d.epilogue;
+  // `symbols` (sntc_conv_forward_columns_dequant): this call's epilogue adds the int32 symbols, which ride in `res`; the plan's
+  // own epilogue is the plain store (columns_error), so schedule, workspace and tiles are the plain column launch's
+  const int epilogue = symbols ? SNTC_EPI_DEQUANT : p2 ? p2->d.epilogue : d.epilogue;
+  if (symbols) res = reinterpret_cast<const float*>(symbols);
   if (epilogue != SNTC_EPI_STORE && !res) return fail(SNTC_ERR_BAD_SHAPE, "epilogue needs `res`");
   if (epilogue == SNTC_EPI_GATE && !aux) return fail(SNTC_ERR_BAD_SHAPE, "gate epilogue needs `aux`");
   Geo g;
@@ -1081,6 +1084,15 @@ extern "C" int sntc_conv_forward_columns(const sntc_conv_plan* p, const float* x
                                          const float* aux, void* workspace, size_t workspace_bytes, void* stream, int ncols) {
   if (const char* why = columns_error(p, ncols)) return fail(SNTC_ERR_UNSUPPORTED, why);
   return conv_forward_impl(p, nullptr, x, n, h, w, y, res, aux, workspace, workspace_bytes, stream, nullptr, ncols);
+}
+
+extern "C" int sntc_conv_forward_columns_dequant(const sntc_conv_plan* p, const float* x, int n, int h, int w, int ncols,
+                                                 const int32_t* symbols, float* y_hat, void* workspace, size_t workspace_bytes,
+                                                 void* stream) {
+  if (const char* why = columns_error(p, ncols)) return fail(SNTC_ERR_UNSUPPORTED, why);
+  if (!symbols || (reinterpret_cast<uintptr_t>(symbols) & 15))
+    return fail(SNTC_ERR_UNSUPPORTED, "sntc_conv_forward_columns_dequant: `symbols` must be a 16-byte aligned int32 tensor");
+  return conv_forward_impl(p, nullptr, x, n, h, w, y_hat, nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, ncols, symbols);
 }
 
 extern "C" int64_t sntc_conv_columns_flops(const sntc_conv_plan* p, int n, int h, int w, int ncols) {

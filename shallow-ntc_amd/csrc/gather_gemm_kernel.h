@@ -103,6 +103,14 @@ __device__ __forceinline__ f32x4 apply_epilogue(f32x4 v, int epi, const f32x4 rs
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = rs[e] >= 0.0f ? v[e] : 0.2f * v[e];
       return v;
+    case SNTC_EPI_DEQUANT: {   // rs: the row load of `res` as for SNTC_EPI_ADD, holding int32 symbols; converted here.  The
+      // whole vector is cast (a bit cast of one element, rs[e], reads the vector's first four bytes for every e)
+      typedef int i32x4 __attribute__((ext_vector_type(4)));
+      const i32x4 s = __builtin_bit_cast(i32x4, rs);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] += (float)s[e];
+      return v;
+    }
     default: return v;
   }
 }
@@ -117,6 +125,7 @@ __device__ __forceinline__ float apply_epilogue1(float v, int epi, const float* 
     case SNTC_EPI_RES_MUL_SQRT: return res[idx] * sqrtf(v);
     case SNTC_EPI_MASK_RELU: return res[idx] > 0.0f ? v : 0.0f;
     case SNTC_EPI_MASK_LEAKY: return res[idx] >= 0.0f ? v : 0.2f * v;
+    case SNTC_EPI_DEQUANT: return v + (float)reinterpret_cast<const int*>(res)[idx];
     default: return v;
   }
 }

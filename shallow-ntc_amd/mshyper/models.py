@@ -618,8 +618,9 @@ class Model:
                 y_hat = grid.dequant(symbols, self._hyper_synthesis.leading_channels(z_hat, symbols.shape[-1]))
             elif self._synthesis.takes_s3(symbols.shape[1], symbols.shape[2]):      # bf16x3: y_hat leaves the dequantisation pre-split
                 y_hat = ops.dequant_split3(symbols, self._hyper_synthesis(z_hat))
-            else:     # mu only: the last hyper-synthesis layer skips its raw-sigma columns where its plan can (same bits)
-                y_hat = ops.dequant_scale_normal(symbols, self._hyper_synthesis.leading_channels(z_hat, symbols.shape[-1]))
+            else:     # mu only: the last hyper-synthesis layer skips its raw-sigma columns where its plan can, and adds the
+                      # symbols in its epilogue (same bits; ops.FUSE_DEQUANT)
+                y_hat = self._hyper_synthesis.dequantised(z_hat, symbols)
             out = self._pixels(y_hat, image_hw, reference)
             if check:
                 ops.check_conv_status()
@@ -640,7 +641,7 @@ class Model:
             y_hats = []
             for st, (z_hat, sym, _hw, _r) in zip(lanes, codes):
                 with ops.fork(cur, st):
-                    y_hats.append(ops.dequant_scale_normal(sym, self._hyper_synthesis.leading_channels(z_hat, sym.shape[-1])))
+                    y_hats.append(self._hyper_synthesis.dequantised(z_hat, sym))
             for st, y_hat in zip(lanes, y_hats):
                 ops.join(cur, st, made=(y_hat,))
             hidden = syn.hidden_many(y_hats)

@@ -24,6 +24,8 @@ WGRAD_STREAM = None         # training: the side stream the weight / bias gradie
 FUSE_RESIDUAL_TAIL = True   # ResidualBlock (c = 192): 3x3 and 1x1 + skip in one launch (bit-identical; False: two launches)
 MEAN_ONLY_HYPER = True      # decode: the hyper-synthesis' last layer computes its mu channels only (ConvPlan.columns; the same bits as the
                             # first half of the whole layer; False: the whole layer, for the A/B and the bit-identity tests)
+FUSE_DEQUANT = True         # decode: that launch also dequantises -- y_hat = symbols + mu leaves its epilogue (ConvPlan.columns(...)(x, symbols=...);
+                            # the same bits as dequant_mean on the stored mu; False: the two launches, for the A/B and the bit-identity tests)
 FUSE_RESIDUAL_BLOCK = not os.environ.get("SNTC_NO_RB_FUSE")   # ResidualBlock (c = 192): head, 3x3 and tail + skip in ONE launch on an 8 x 32
                             # pixel tile with its halo patch in LDS (csrc/rb_kernel.h on the fp32 policy of csrc/rb_fused.hip; bit-identical to the three launches)
 FUSED_BLOCK_MIN_TILES = 256  # ... where the launch offers at least one 8 x 32 tile per CU (one workgroup per CU); below, the layers
@@ -580,7 +582,9 @@ class ConvPlan:
             capi.call("sntc_conv_plan_set_choice", self._h, int(n), int(h), int(w), int(variant), int(bool(stream_k)))
         self._tuned[(int(n), int(h), int(w))] = (int(variant), int(bool(stream_k)))
 
-    def __call__(self, x, res=None, aux=None, out=None):
+    def __call__(self, x, res=None, aux=None, out=None, symbols=None):
+        """``symbols`` (a ``columns`` view only): int32, the output's shape -- the launch returns y_hat = symbols + self(x), the
+        decoder's dequantisation in its epilogue (sntc_conv_forward_columns_dequant; the bits of ``dequant_mean(symbols, self(x))``)."""
         if self.s3:
             _check_s3(x, self.cin)
         else:
@@ -588,9 +592,14 @@ class ConvPlan:
         n, h, w = x.shape[:3]
         ho, wo = self.out_hw(h, w)
         y = out if out is not None else torch.empty((n, ho, wo, self.cout), dtype=torch.float32, device=x.device)
-        for t in (res, aux):
+        for t in (res, aux, symbols):
             if t is not None and tuple(t.shape) != tuple(y.shape):
                 raise ValueError(f"epilogue operand shape {tuple(t.shape)} != output shape {tuple(y.shape)}")
+        if symbols is not None:
+            if not self._ncols or res is not None or aux is not None:
+                raise capi.SntcError(capi.ERR_UNSUPPORTED, "symbols: a column-limited view's own epilogue, without res / aux")
+            if symbols.dtype != torch.int32 or not symbols.is_contiguous() or symbols.device != x.device:
+                raise ValueError("symbols: a contiguous int32 tensor on the input's device")
         if x.numel() * x.element_size() >= MAX_INPUT_BYTES and n > 1:
             # the kernel addresses its input with 32-bit buffer offsets: split the batch (images are independent)
             half = n // 2
@@ -598,10 +607,12 @@ class ConvPlan:
             r1 = None if res is None else res[half:]
             a0 = None if aux is None else aux[:half]
             a1 = None if aux is None else aux[half:]
-            self.__call__(x[:half], r0, a0, out=y[:half])
-            self.__call__(x[half:], r1, a1, out=y[half:])
+            s0 = None if symbols is None else symbols[:half]
+            s1 = None if symbols is None else symbols[half:]
+            self.__call__(x[:half], r0, a0, out=y[:half], symbols=s0)
+            self.__call__(x[half:], r1, a1, out=y[half:], symbols=s1)
             return y
-        if AUTOTUNE and (n, h, w) not in self._tuned:
+        if AUTOTUNE and (n, h, w) not in self._tuned:     # the plain launch is what is measured, with symbols as well
             self.tune(x, res, aux, reps=AUTOTUNE)
         if LAUNCH_LOG is not None:
             LAUNCH_LOG.append((self, int(n), int(h), int(w)))
@@ -612,8 +623,12 @@ class ConvPlan:
         if self._ncols:      # the workspace is asked for the column count that is launched: the stream-K partition depends on it
             ws_bytes = int(capi.load().sntc_conv_columns_workspace_bytes(self._h, n, h, w, self._ncols))
             ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=x.device) if ws_bytes else None
-            capi.call("sntc_conv_forward_columns", self._h, _ptr(x), n, h, w, _ptr(y), _ptr(res), _ptr(aux), _ptr(ws), ws_bytes, _stream(),
-                      self._ncols)
+            if symbols is not None:
+                capi.call("sntc_conv_forward_columns_dequant", self._h, _ptr(x), n, h, w, self._ncols, _ptr(symbols), _ptr(y), _ptr(ws),
+                          ws_bytes, _stream())
+            else:
+                capi.call("sntc_conv_forward_columns", self._h, _ptr(x), n, h, w, _ptr(y), _ptr(res), _ptr(aux), _ptr(ws), ws_bytes,
+                          _stream(), self._ncols)
         else:
             ws_bytes = int(capi.load().sntc_conv_workspace_bytes(self._h, n, h, w))
             ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=x.device) if ws_bytes else None
@@ -627,7 +642,7 @@ class ConvPlan:
             prof.append(dict(e0=e0, e1=e1, flops=(self.parent if self._ncols else self).flops(n, h, w), launched_flops=self.flops(n, h, w),
                              variant=v, nblocks=nb, vec=self.cin % 16 == 0 or self.rowpack,
                              kind=self.kind, k=self.k[0], s=self.stride, cin=self.cin, cout=self.cout, n=n, h=h, w=w,
-                             colm=self.launch_order(n, h, w)))
+                             colm=self.launch_order(n, h, w), dequant=symbols is not None))
         return y
 
 
@@ -1312,6 +1327,14 @@ def dequant_scale_normal(symbols, hyper):
     else:
         capi.call("sntc_dequant_scale_normal", _ptr(symbols), _ptr(hyper), n, hw, c, _ptr(y_hat), _stream())
     return y_hat
+
+
+def dequant_mean(symbols, mu):
+    """y_hat = symbols + mu for a compact mu (c channels: what a mean-only hyper-synthesis stores): ``dequant_scale_normal``'s
+    sntc_dequant_mean form, and the reference of the launch that dequantises in its epilogue (``FUSE_DEQUANT``)."""
+    if mu.shape[-1] != symbols.shape[-1]:
+        raise ValueError(f"dequant_mean: mu {tuple(mu.shape)} is not compact for symbols {tuple(symbols.shape)}")
+    return dequant_scale_normal(symbols, mu)
 
 
 def _check_step_inputs(a, hyper, per_image):

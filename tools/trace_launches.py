@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-launch durations of the gather-GEMM and synthesis kernels in a rocprofv3 kernel trace, grouped by (kernel, workgroups):
+"""Per-launch durations of the decode's kernels (gather GEMM and its split-K finish, synthesis, dequantisation, output layer,
+zeroing) in a rocprofv3 kernel trace, grouped by (kernel, workgroups):
 
     python tools/trace_launches.py <..._kernel_trace.csv>
 
@@ -10,7 +11,7 @@ rows=list(csv.DictReader(open(f)))
 k=collections.defaultdict(list)
 for r in rows:
     name=r["Kernel_Name"]
-    if "gg_kernel" not in name and "syn_kernel" not in name: continue
+    if not any(w in name for w in ("gg_kernel", "syn_kernel", "gg_reduce_kernel", "dequant_kernel", "two_layer_tail_kernel", "zero_words_kernel")): continue
     short=re.sub(r"\(sntc.*","",name.replace("void sntc::",""))
     grid=int(r["Grid_Size_X"] if "Grid_Size_X" in r else r["Grid_Size"])//int(r.get("Workgroup_Size_X") or r.get("Workgroup_Size"))
     k[(short,grid)].append((int(r["End_Timestamp"])-int(r["Start_Timestamp"]))/1e3)
