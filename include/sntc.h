@@ -603,6 +603,38 @@ int sntc_step_map_ladder_cost(const float* y, const float* mu, int n, int64_t hw
                               int ntables, int total_entries, const uint32_t* cost_q, uint64_t* cost, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Rate-distortion optimised quantisation (csrc/rdoq.hip, rule in csrc/rdoq_rules.h; DESIGN.md 4.7 "RDOQ").  The reference
+ *   rounds y - mu to the nearest integer (mshyper/models.py:273-279) and so do the step kernels above; these two choose, per
+ *   element, among the nearest integer and its neighbours towards zero by exact rate + weighted squared error.  With the three
+ *   rules above, d = y - mu, u = d * inv_step (float32), s0 = (int)rintf(u), t = clamp(base id - k, 0, 63) and
+ *   price(s) = cost_q[offset_t + symbol of s in table t] (sntc_rans_cost's entry, ESCAPE included):
+ *     enable[image] == 0 or s0 == 0:  symbol = s0
+ *     else the candidates, in order:  s0;  a = s0 - sign(s0);  0, if flags & 1 and a != 0
+ *       J(s) = fadd(fmul(weight[channel], fmul(e, e)), (float)price(s)),  e = fsub(u, (float)s)
+ *       every operation one float32 rounding, nothing fused; the smallest J wins, a later candidate only on strict <
+ *       (a NaN J never displaces s0, a tie keeps the nearer symbol)
+ *   table_ids are those sntc_step_symbols / sntc_step_map_symbols write: the symbols go into ordinary wire format 3 / 5 / 7.
+ *   With every enable 0 the outputs are those entry points', bit for bit.  s0 is the nearest integer, so with weight >= 0 a
+ *   change is always to a strictly cheaper symbol: per image sntc_rans_cost of these symbols <= that of the plain ones, < where
+ *   changed > 0.
+ *   weight float [c] (cost_q units, 2^-16 bit, per squared symbol-unit error), enable int32 [n], both on the device; meta /
+ *   ntables / total_entries / cost_q as sntc_rans_cost, the set holding the ladder's 64 tables first (ntables >= 64); staged in
+ *   LDS where they fit, read from memory otherwise, same result.  changed (optional, may be null) int32 [n], zeroed by the call:
+ *   the elements of each image written != s0, an exact integer whatever the launch geometry.  y / mu / symbols / weight
+ *   16-byte aligned, the id arrays 8-byte aligned, c % 4 == 0, mu_stride >= c and % 4 == 0, 1 <= n <= 65535 (checked,
+ *   SNTC_ERR_BAD_SHAPE before any launch).
+ * ------------------------------------------------------------------------------------------------------- */
+int sntc_rdoq_symbols(const float* y, const float* mu, int n, int64_t hw, int c, int mu_stride, const uint16_t* base_ids,
+                      const float* inv_step, const int32_t* shift, const float* weight, const int32_t* enable, int flags,
+                      const uint32_t* meta, int ntables, int total_entries, const uint32_t* cost_q, int32_t* symbols,
+                      uint16_t* table_ids, int32_t* changed, void* stream);
+/* The same with k and inv_step per latent position: kmap int8 [n][hw], lut float [2][65] as in sntc_step_map_symbols. */
+int sntc_rdoq_map_symbols(const float* y, const float* mu, int n, int64_t hw, int c, int mu_stride, const uint16_t* base_ids,
+                          const int8_t* kmap, const float* lut, const float* weight, const int32_t* enable, int flags,
+                          const uint32_t* meta, int ntables, int total_entries, const uint32_t* cost_q, int32_t* symbols,
+                          uint16_t* table_ids, int32_t* changed, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Requantisation: the symbols of a coarser step from the symbols a file holds, without y and without pixels
  *   (csrc/quant_step.hip, DESIGN.md 4.7 "transcode").  The reference quantises once, from y, with step 1
  *   (mshyper/models.py:273-279) and has no second rate; here the source is what its decoder would hand the synthesis.  Per

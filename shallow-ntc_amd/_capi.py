@@ -163,6 +163,10 @@ SIGNATURES = {
     "sntc_dequant_step_map": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "sntc_step_map_ladder_cost": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int,
                                             C.c_int, _P, _P, _P]),
+    "sntc_rdoq_symbols": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P,
+                                    _P, _P, _P, _P]),
+    "sntc_rdoq_map_symbols": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int,
+                                        _P, _P, _P, _P, _P]),
     "sntc_step_requant_symbols": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "sntc_step_requant_ladder_cost": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int,
                                                 C.c_int, _P, _P, _P]),

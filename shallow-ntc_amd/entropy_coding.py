@@ -787,6 +787,71 @@ def require_fp32(precision, what):
         raise NotImplementedError(f"{what} runs in precision 'fp32', not {precision!r}: the pre-split dequantisation is not extended")
 
 
+RDOQ_TRY_ZERO = 1                         # flags bit 0 of the RDOQ kernels: also try the symbol 0 (csrc/rdoq_rules.h)
+
+
+def rdoq_weights(lam, gains, strength=1.0):
+    """The per-channel weight of the RDOQ kernels, a pure function: -> float32 [c] = strength * COST_UNIT * lam * gains / 3, in
+    cost_q units (2^-16 bit) per squared symbol-unit error.  J = bits / (H W) + lam * SSE / (3 H W) times COST_UNIT H W is
+    cost_q + COST_UNIT lam SSE / 3, and a symbol-unit error e in channel c moves the SSE by about gains[c] e^2 step^2
+    (``Model.latent_gains``: a linearisation at zero latents, cross terms ignored); with lam_i = lam / step_i^2 (``step_lambdas``)
+    the step cancels, so one weight serves every step.  ValueError: a strength or lam that is not positive and finite, gains
+    that are not a vector of finite non-negative numbers."""
+    s, l = float(strength), float(lam)
+    if not (np.isfinite(s) and s > 0):
+        raise ValueError(f"rdoq: strength must be positive and finite, not {strength!r}")
+    if not (np.isfinite(l) and l > 0):
+        raise ValueError(f"rdoq: lambda must be positive and finite, not {lam!r}")
+    g = np.asarray(gains, np.float64)
+    if g.ndim != 1 or not g.size or not np.isfinite(g).all() or (g < 0).any():
+        raise ValueError("rdoq: gains must be a vector of finite, non-negative numbers, one per latent channel")
+    with np.errstate(over="ignore"):
+        return (s * float(COST_UNIT) * l * g / 3.0).astype(np.float32)
+
+
+class Rdoq:
+    """What ``StepGrid.symbols`` needs to choose symbols by rate + weighted squared error instead of by distance (csrc/rdoq.hip,
+    DESIGN.md 4.7 "RDOQ"): ``weight`` float32 [c] (``rdoq_weights``), ``enable`` one 0 / 1 per image (None: every image), ``zero``
+    (also try the symbol 0), ``tables`` the coder's ``DeviceTables`` of the scale ladder.  Host state; the two small arrays go up
+    on first use (``on``) in ONE copy.  ``changed``: int32 [n] on the device after a launch, the elements per image that were
+    not written as their nearest integer."""
+
+    def __init__(self, weight, n, tables, enable=None, zero=True):
+        self.weight = np.ascontiguousarray(weight, np.float32)
+        if self.weight.ndim != 1:
+            raise ValueError("Rdoq: weight float32 [c], one per latent channel")
+        self.n, self.tables, self.zero, self.changed, self._on = int(n), tables, bool(zero), None, None
+        self.enable = check_enable(enable, self.n)
+
+    @property
+    def flags(self):
+        return RDOQ_TRY_ZERO if self.zero else 0
+
+    def set_enable(self, enable):
+        """Another per-image enable list (``check_enable``); the next launch uploads it."""
+        enable = check_enable(enable, self.n)
+        if enable != self.enable:
+            self.enable, self._on = enable, None
+        return self
+
+    def on(self, device):
+        """-> (weight float32 [c], enable int32 [n]) on ``device``, uploaded once."""
+        device = torch.device(device)
+        if self._on is None or self._on[0] != device:
+            self._on = (device, tuple(pack_upload([self.weight, np.asarray(self.enable, np.int32)], device)[1]))
+        return self._on[1]
+
+
+def check_enable(enable, n):
+    """A per-image enable list of the RDOQ kernels -> [0 | 1] * n (None: all ones).  ValueError on another length or value."""
+    if enable is None:
+        return [1] * n
+    vals = list(enable)
+    if len(vals) != n or any(not isinstance(v, (bool, int, np.integer, np.bool_)) or int(v) not in (0, 1) for v in vals):
+        raise ValueError(f"rdoq: enable must hold one 0 / 1 per image ({n}), not {enable!r}")
+    return [int(v) for v in vals]
+
+
 class StepGrid:
     """How y - mu of a batch of n images is quantised (csrc/quant_step.hip): ``kind`` "unit" (step 1, wire format
     3), "image" (``steps``: one ladder index per image, format 5) or "map" (``kmap``: the absolute index of every latent position,
@@ -854,8 +919,19 @@ class StepGrid:
             self._on = (device, t)
         return self._on[1]
 
-    def symbols(self, y, hyper):
-        """-> (y's symbols int32, their table ids)."""
+    def symbols(self, y, hyper, rdoq=None):
+        """-> (y's symbols int32, their table ids).  ``rdoq`` (an ``Rdoq``): the images it enables take, per element, the
+        candidate with the smallest rate + weighted squared error (csrc/rdoq.hip) and ``rdoq.changed`` counts them; the others,
+        and every image without it, the nearest integer.  A unit grid then goes through the per-image kernel at step 1, shift 0."""
+        if rdoq is not None:
+            w, en = rdoq.on(y.device)
+            if self.kind == "map":
+                out = ops.rdoq_map_symbols(y, hyper, scale_table_ids(hyper), *self.on(y.device), w, en, rdoq.flags, rdoq.tables)
+            else:
+                t = self.on(y.device) if self.kind == "image" else self._unit_steps(y.device)
+                out = ops.rdoq_symbols(y, hyper, scale_table_ids(hyper), t[1], t[2], w, en, rdoq.flags, rdoq.tables)
+            rdoq.changed = out[2]
+            return out[:2]
         if self.kind == "unit":
             sym = ops.entropy_scale_normal(y, hyper, want_symbols=True)[2]
             return sym, scale_table_ids(hyper)
@@ -863,6 +939,13 @@ class StepGrid:
         if self.kind == "image":
             return ops.step_symbols(y, hyper, scale_table_ids(hyper), t[1], t[2])
         return ops.step_map_symbols(y, hyper, scale_table_ids(hyper), *t)
+
+    def _unit_steps(self, device):
+        """``step_tensors`` of a unit grid (step 1, shift 0 per image), for the one kernel that has no unit form (RDOQ); kept."""
+        device = torch.device(device)
+        if getattr(self, "_unit_on", None) is None or self._unit_on[0] != device:
+            self._unit_on = (device, tuple(step_tensors([0] * self.n, device)))
+        return self._unit_on[1]
 
     def table_ids(self, base_ids):
         """The decoder's table ids from ``scale_table_ids``: the tables K places down the ladder, its start tables unchanged."""
@@ -1361,21 +1444,46 @@ class Codec:
         zi = round_to_int(z)
         return zi, self.m._hyper_synthesis(int_to_float(zi))
 
-    def _symbols(self, z, y, grid, pre=None):
+    def _symbols(self, z, y, grid, pre=None, rdoq=None):
         """(z_loc, y_loc) -> what the file carries: (zi int32, z's table ids, y symbols int32, y's table ids, hyper).
-        ``grid``: the ``StepGrid`` y - mu is quantised on; ``pre``: ``_hyper_of(z)`` if the caller has it."""
+        ``grid``: the ``StepGrid`` y - mu is quantised on; ``pre``: ``_hyper_of(z)`` if the caller has it; ``rdoq``: an ``Rdoq``
+        (``self.rdoq``) -- the images it enables are quantised by rate + distortion (``StepGrid.symbols``)."""
         m = self.m
         grid.on(m.device)                                          # its upload, if any, before anything is enqueued
+        if rdoq is not None:
+            rdoq.on(m.device)
+            if grid.kind == "unit":
+                grid._unit_steps(m.device)
         zi, hyper = self._hyper_of(z) if pre is None else pre
         ztid = channel_table_ids(z.shape, m.device)
-        sym, ytid = grid.symbols(y, hyper)
+        sym, ytid = grid.symbols(y, hyper) if rdoq is None else grid.symbols(y, hyper, rdoq)
         return zi, ztid, sym, ytid, hyper
 
-    def _launch_latents(self, z, y, image_hw, grid, pre=None):
+    def rdoq(self, weight, n, enable=None, zero=True):
+        """The ``Rdoq`` of this codec's y tables for a batch of n images: ``weight`` float32 [C] (``rdoq_weights``), ``enable``
+        one 0 / 1 per image (None: all), ``zero``: also try the symbol 0.  ValueError on a weight that is not one per channel."""
+        r = Rdoq(weight, n, self.y_tables, enable, zero)
+        if r.weight.shape != (self.m._bottleneck_size,):
+            raise ValueError(f"rdoq: {r.weight.shape} weights for {self.m._bottleneck_size} latent channels")
+        return r
+
+    def _rdoq_of(self, rdoq, rdoq_enable, n):
+        """``rdoq`` / ``rdoq_enable`` of the public entry points -> the ``Rdoq`` to launch with, or None.  Every refusal here:
+        before anything is enqueued."""
+        if rdoq is None:
+            if rdoq_enable is not None:
+                raise ValueError("rdoq_enable needs rdoq")
+            return None
+        if not isinstance(rdoq, Rdoq) or rdoq.n != n:
+            raise ValueError(f"rdoq: an entropy_coding.Rdoq for {n} images (Codec.rdoq)")
+        require_fp32(self.m._precision, "rate-distortion optimised quantisation")
+        return rdoq if rdoq_enable is None else rdoq.set_enable(rdoq_enable)
+
+    def _launch_latents(self, z, y, image_hw, grid, pre=None, rdoq=None):
         """The device half of ``compress_latents`` on the current stream, no host synchronisation.  ``grid`` travels in the
-        file."""
+        file; ``rdoq`` as in ``_symbols``: nothing of it travels, the file is that of its symbols."""
         n, H, W = self._check_latents(z, y, image_hw)
-        zi, ztid, sym, ytid, _ = self._symbols(z, y, grid, pre)
+        zi, ztid, sym, ytid, _ = self._symbols(z, y, grid, pre, rdoq)
         sz, sy = _segments(zi[0].numel()), _segments(sym[0].numel())
         lz, ly = _lanes(-(-zi[0].numel() // sz)), _lanes(-(-sym[0].numel() // sy))
         dims = (y.shape[-1], z.shape[-1], z.shape[1], z.shape[2], y.shape[1], y.shape[2])
@@ -1398,27 +1506,33 @@ class Codec:
             out.append(j["grid"].pack(*fields) + zwords.tobytes() + ywords.tobytes())
         return out
 
-    def compress_latents(self, z_loc, y_loc, image_hw, step=None, step_offsets=None) -> bytes:
+    def compress_latents(self, z_loc, y_loc, image_hw, step=None, step_offsets=None, rdoq=None, rdoq_enable=None) -> bytes:
         """Latents of this model for images of ``image_hw`` = (H, W) -- the encoder's, or ones refined by iterative inference --
         -> the bitstream ``decompress`` reads: z is rounded, the hyper-synthesis gives mu / the scale indexes, y - mu is rounded,
         both are coded.  ``compress(x)`` is this on ``infer_latent_rvs(x)``.  ``step``: an index on the scale ladder, or one per
         image: y - mu is quantised with the step ``step_size(k)`` and coded with the tables k places down the ladder (wire
         format 5; with every index 0 the v3 blob of ``step=None``, byte for byte).  ``step_offsets``: integers [n, h, w] at latent
         resolution, added to the image's step per position and clipped to the ladder (wire format 7 where the result varies
-        inside an image; a constant result is the v5 / v3 blob of those indexes, byte for byte)."""
+        inside an image; a constant result is the v5 / v3 blob of those indexes, byte for byte).  ``rdoq`` (``self.rdoq(...)``):
+        the symbols of the images it enables are chosen by rate + weighted squared error (csrc/rdoq.hip) -- the same wire
+        format, read by the same decoder; ``rdoq_enable``: one 0 / 1 per image instead of its own list.  ``rdoq.changed``
+        then counts, per image, the symbols that are not the nearest integer."""
         m = self.m
         grid = self._grid(step, step_offsets, z_loc.shape[0], int(image_hw[0]), int(image_hw[1]))
+        rdoq = self._rdoq_of(rdoq, rdoq_enable, z_loc.shape[0])
         with torch.cuda.device(m.device):
-            return self._finish([self._launch_latents(z_loc.contiguous(), y_loc.contiguous(), image_hw, grid)])[0]
+            return self._finish([self._launch_latents(z_loc.contiguous(), y_loc.contiguous(), image_hw, grid, rdoq=rdoq)])[0]
 
-    def latents_cost(self, z_loc, y_loc, x, step=None, step_offsets=None):
+    def latents_cost(self, z_loc, y_loc, x, step=None, step_offsets=None, rdoq=None, rdoq_enable=None, pre=None):
         """What ``compress_latents`` would write for these latents and what ``decompress`` would make of it, without writing it:
         -> (cost_z, cost_y int64 [n] in 2^-16 bit (``rans_cost``), uint8 pixels, integer SSE [n] against ``x``), all on the
-        device, no host synchronisation.  ``step`` / ``step_offsets`` as in ``compress_latents``."""
+        device, no host synchronisation.  ``step`` / ``step_offsets`` / ``rdoq`` / ``rdoq_enable`` as in ``compress_latents``
+        (``rdoq.changed``: int32 [n] on the device afterwards).  ``pre``: ``_hyper_of(z_loc)`` if the caller has it."""
         m = self.m
         n, H, W = self._check_latents(z_loc, y_loc, x.shape[1:3])
         grid = self._grid(step, step_offsets, n, H, W)
-        zi, ztid, sym, ytid, hyper = self._symbols(z_loc.contiguous(), y_loc.contiguous(), grid)
+        rdoq = self._rdoq_of(rdoq, rdoq_enable, n)
+        zi, ztid, sym, ytid, hyper = self._symbols(z_loc.contiguous(), y_loc.contiguous(), grid, pre, rdoq)
         cost_z, cost_y = rans_cost(zi, ztid, self.z_tables), rans_cost(sym, ytid, self.y_tables)
         y_hat = grid.dequant(sym, hyper, m._synthesis.takes_s3(sym.shape[1], sym.shape[2]))
         px, sse = m._pixels(y_hat, (H, W), x)                     # the decoder's own steps from the symbols on

@@ -247,6 +247,7 @@ class Model:
         self._prior_weights = pw
         self._prior = None
         self._codec = None
+        self._latent_gains = None
 
     def _prior_channels(self):
         return self._hyper_bottleneck_size
@@ -680,7 +681,8 @@ class Model:
             self._codec = Codec(self)
         return self._codec
 
-    def compress(self, x, itinf=None, step=None, target_bpp=None, step_offsets=None, target_psnr=None, max_error=None) -> bytes:
+    def compress(self, x, itinf=None, step=None, target_bpp=None, step_offsets=None, target_psnr=None, max_error=None,
+                 rdoq=None) -> bytes:
         """Images -> self-contained bitstream (rANS over the integer CDF tables of both entropy models).
         ``itinf`` = dict(steps, seed=0, check_every=None): refine the latents of THESE images by SGA iterative inference first
         (``initialize_itinf`` + ``steps`` x ``itinf_train_step(x, seed=seed, fetch=False)`` under the model's own tau / learning-rate
@@ -742,11 +744,30 @@ class Model:
         pixels within max_error of x quantised to uint8, that picture itself at 0.  Byte for byte
         ``add_residual(compress(x, ...), x, max_error)``.  ``last_compress_report`` gains, per image, max_error,
         residual_bits_predicted and residual_tables (a plain ``compress(x, max_error=d)`` reports just these).  Mean-scale
-        hyperprior models in precision 'fp32' only."""
+        hyperprior models in precision 'fp32' only.
+        ``rdoq`` (True, or dict(strength=1.0, zero=True, gains=None)): rate-distortion optimised quantisation -- one streaming
+        pass over the latents (csrc/rdoq.hip) between "round to nearest" and SGA refinement.  Per element whose nearest integer
+        s0 is not 0 the symbol is the candidate among s0, s0 - sign(s0) and (``zero``) 0 with the smallest
+        w_c (u - s)^2 + cost_q(s): cost_q the exact integer price of the symbol under the element's own table, u = (y - mu) /
+        step, w_c = strength 65536 lambda g_c / 3 with lambda the scheduled rd_lambda and g_c = ``gains`` (default
+        ``latent_gains()``: what a unit change of channel c does to the SSE of the pixels, a linearisation -- a modelling choice,
+        not a measured optimum).  The weight does not depend on the step: image i is judged with lambda_i = lambda /
+        step_size(k_i)^2 as ``itinf`` at a step judges (on a step map: the weighted D_w of ``coded_cost(weighted=True)``).  The
+        guard is ``itinf``'s: one analysis and one hyper-synthesis, then the plain and the RDOQ candidate go through the exact
+        coded cost (``coded_cost``: bits of the coder's tables, integer SSE of the decoded pixels), and image i is coded with
+        RDOQ only where J_rdoq < J_plain -- never a worse file, by J, than without it, per image.  The file is ordinary wire
+        format 3 / 5 / 7.  ``last_compress_report``: per image rdoq_used, changed (the RDOQ candidate's symbols that are not the
+        nearest integer), bits_plain, bits_rdoq, sse_plain, sse_rdoq, J_plain, J_rdoq, J_chosen, lam, quant_step.  Combines
+        with ``step``, ``step_offsets`` and ``max_error``; excludes ``itinf``, ``target_bpp`` and ``target_psnr`` (ValueError: the
+        ladder kernels price nearest-integer symbols).  Mean-scale hyperprior models in precision 'fp32' with MSE only
+        (NotImplementedError)."""
         if max_error is not None:
             self._check_residual_arguments("compress", max_error)
         self._check_step_arguments("compress", step, target_bpp, itinf, step_offsets, target_psnr=target_psnr)
-        if itinf is not None:
+        cfg = None if rdoq is None else self._check_rdoq_arguments("compress", rdoq, itinf, target_bpp, target_psnr)
+        if cfg is not None:
+            blob = self._compress_rdoq(x, cfg, step, step_offsets)
+        elif itinf is not None:
             if "target_psnr" in itinf:
                 raise ValueError("compress: target_psnr is not implemented inside itinf")
             blob = self._compress_itinf(x, **itinf)
@@ -759,8 +780,107 @@ class Model:
                 self.last_compress_report = codec.last_report
         if max_error is None:
             return blob
-        reported = itinf is not None or target_bpp is not None or target_psnr is not None
+        reported = itinf is not None or target_bpp is not None or target_psnr is not None or cfg is not None
         return self._add_residual(blob, x, max_error, self.last_compress_report if reported else None)
+
+    def _check_rdoq_arguments(self, where, rdoq, itinf=None, target_bpp=None, target_psnr=None):
+        """The refusals of ``rdoq`` that need no image, every one before any launch: -> None (off), or the checked
+        dict(strength, zero, gains) -- gains float64 [c], or None for ``latent_gains()``."""
+        if rdoq is None or rdoq is False:
+            return None
+        if self.factorized:
+            raise NotImplementedError(f"{where}(rdoq): the symbols are priced with the scale ladder's normal tables; mean-scale "
+                                      "hyperprior models only, not a factorized-prior model")
+        if itinf is not None or target_bpp is not None or target_psnr is not None:
+            raise ValueError(f"{where}: rdoq excludes itinf, target_bpp and target_psnr (the ladder kernels price nearest-integer symbols)")
+        require_fp32(self._precision, f"{where}(rdoq)")
+        if self._distortion == "ms_ssim":
+            raise NotImplementedError(f"{where}(rdoq): the weights are those of a squared pixel error, not distortion='ms_ssim'")
+        if rdoq is True:
+            rdoq = {}
+        if not isinstance(rdoq, dict) or set(rdoq) - {"strength", "zero", "gains"}:
+            raise ValueError(f"{where}: rdoq is True or dict(strength=1.0, zero=True, gains=None), not {rdoq!r}")
+        cfg = dict(strength=rdoq.get("strength", 1.0), zero=bool(rdoq.get("zero", True)), gains=rdoq.get("gains"))
+        from ..entropy_coding import rdoq_weights
+        c = self._bottleneck_size
+        try:
+            gains = None if cfg["gains"] is None else np.asarray(cfg["gains"], np.float64)
+            cfg["strength"] = float(cfg["strength"])
+        except (TypeError, ValueError):
+            raise ValueError(f"{where}: rdoq strength a number, gains {c} numbers") from None
+        if gains is not None and gains.shape != (c,):
+            raise ValueError(f"{where}: rdoq gains must hold one number per latent channel ({c}), not shape {gains.shape}")
+        rdoq_weights(1.0, np.zeros(c) if gains is None else gains, cfg["strength"])      # its checks: strength, the gains' values
+        cfg["gains"] = gains
+        return cfg
+
+    def _rdoq_tool(self, cfg, n):
+        """The checked dict of ``rdoq`` -> the ``entropy_coding.Rdoq`` of n images, every image enabled."""
+        from ..entropy_coding import rdoq_weights
+        gains = self.latent_gains() if cfg["gains"] is None else cfg["gains"]
+        weight = rdoq_weights(float(self._scheduled_rd_lambda), gains, cfg["strength"])
+        return self._get_codec().rdoq(weight, n, zero=cfg["zero"])
+
+    def latent_gains(self):
+        """What a unit change of one latent channel does to the squared error of the pixels: float64 [c], cached per set of
+        weights.  g_c = sum over pixels and colours of (255 (syn(e_c) - syn(0)))^2 on the synthesis' float output, before any
+        uint8 rounding, e_c a unit impulse in channel c at the centre of a 9 x 9 grid of zero latents; the c impulses and the
+        zero grid run as ONE decoder batch of c + 1 latents.  The response must be exactly zero over the outermost ring of
+        latent positions -- the impulse response then lies wholly inside the grid -- else RuntimeError.
+        A linearisation of the synthesis AT ZERO LATENTS with the cross terms between channels and positions ignored: a stated
+        modelling choice for the weights of ``compress(x, rdoq=...)``, not a measured optimum."""
+        if getattr(self, "_latent_gains", None) is None:
+            c, side = self._bottleneck_size, 9
+            y = np.zeros((c + 1, side, side, c), np.float32)
+            y[np.arange(c), side // 2, side // 2, np.arange(c)] = 1.0
+            with torch.cuda.device(self.device):
+                out = self._synthesis(ops.to_device(y, self.device)).cpu().numpy().astype(np.float64)
+                ops.check_conv_status()
+            if out.shape[1] % side or out.shape[2] % side:
+                raise RuntimeError(f"latent_gains: a {out.shape[1]} x {out.shape[2]} picture from {side} x {side} latent positions")
+            d = 255.0 * (out[:c] - out[c:])
+            bh, bw = out.shape[1] // side, out.shape[2] // side
+            ring = d.copy()
+            ring[:, bh:-bh, bw:-bw] = 0.0
+            if np.any(ring != 0.0):
+                raise RuntimeError("latent_gains: the synthesis' impulse response reaches the outermost ring of a 9 x 9 latent grid; "
+                                   "the gains would be truncated")
+            self._latent_gains = (d * d).reshape(c, -1).sum(axis=1)
+        return self._latent_gains.copy()
+
+    def _compress_rdoq(self, x, cfg, step, step_offsets):
+        """``compress(x, rdoq=...)``: the plain and the RDOQ candidate judged by exact coded cost, the file coded with RDOQ on
+        the images it wins."""
+        x = self._as_device_images(x)
+        n, H, W = x.shape[0], int(x.shape[1]), int(x.shape[2])
+        codec = self._get_codec()
+        grid = codec._grid(step, step_offsets, n, H, W)                  # ValueError before any launch
+        lam = float(self._scheduled_rd_lambda)
+        if grid.kind == "map":                                           # the weight sits on every position's pixels (D_w)
+            from ..entropy_coding import check_steps
+            ks, lams = check_steps(0 if step is None else step, n), np.full(n, lam)
+            cost_kw = dict(step=step, step_offsets=step_offsets, weighted=True, lam=None)
+        else:
+            ks = grid.steps or [0] * n
+            lams = step_lambdas(lam, ks)
+            cost_kw = dict(step=ks if any(ks) else None, step_offsets=None, weighted=False, lam=lams)
+        tool = self._rdoq_tool(cfg, n)
+        with torch.cuda.device(self.device):
+            lat = self.infer_latent_rvs(x)
+            z, y = lat.uq[0].loc.contiguous(), lat.uq[1].loc.contiguous()
+            pre = codec._hyper_of(z)
+            plain = self._coded_cost(x, lat, pre=pre, **cost_kw)
+            cand = self._coded_cost(x, lat, rdoq=tool, pre=pre, **cost_kw)
+            used = cand["J"] < plain["J"]                                # strictly better only: the nearest integers win a tie
+            tool.set_enable([int(u) for u in used])
+            blob = codec._finish([codec._launch_latents(z, y, (H, W), grid, pre, rdoq=tool if used.any() else None)])[0]
+        pick = lambda key, i: float((cand if used[i] else plain)[key][i])
+        self.last_compress_report = [
+            dict(rdoq_used=bool(used[i]), changed=int(cand["changed"][i]), bits_plain=float(plain["bits"][i]),
+                 bits_rdoq=float(cand["bits"][i]), sse_plain=float(plain["sse"][i]), sse_rdoq=float(cand["sse"][i]),
+                 J_plain=float(plain["J"][i]), J_rdoq=float(cand["J"][i]), J_chosen=pick("J", i), bits_chosen=pick("bits", i),
+                 sse_chosen=pick("sse", i), lam=float(lams[i]), quant_step=int(ks[i])) for i in range(n)]
+        return blob
 
     def _check_residual_arguments(self, where, max_error):
         """The refusals of the residual layer that need no image: every one before any launch."""
@@ -851,7 +971,7 @@ class Model:
             raise NotImplementedError("step_offsets_shape: a factorized-prior model takes no step_offsets; mean-scale hyperprior models only")
         return tuple(int(v) for v in self._get_codec().latent_shapes(int(H), int(W))[4:])
 
-    def coded_cost(self, x, latent_rvs=None, step=None, lam=None, step_offsets=None, weighted=False):
+    def coded_cost(self, x, latent_rvs=None, step=None, lam=None, step_offsets=None, weighted=False, rdoq=None):
         """Per image, the cost of what ``decompress`` will output for ``latent_rvs`` (None: the encoder's latents of x) coded at
         ``step`` (None: step 1; a ladder index or one per image as in ``compress``), without
         writing a file: dict of float64 arrays [n] -- ``bits_z`` / ``bits_y`` = ``entropy_coding.rans_cost`` of the symbols the
@@ -869,7 +989,16 @@ class Model:
         ``sse_blocks`` is also a region-of-interest metric.  The PSNR of the decoded pixels inside a block mask (bool [hb, wb],
         e.g. ``step_offsets[i, :hb, :wb] == inside``; edge blocks hold fewer pixels, so count them):
             rows = np.minimum(B, H - B * np.arange(hb))[:, None]; cols = np.minimum(B, W - B * np.arange(wb))[None, :]
-            mse = sse_blocks[i][mask].sum() / (3.0 * (rows * cols)[mask].sum()); psnr = 10 * np.log10(255.0 ** 2 / mse)"""
+            mse = sse_blocks[i][mask].sum() / (3.0 * (rows * cols)[mask].sum()); psnr = 10 * np.log10(255.0 ** 2 / mse)
+        ``rdoq`` (True or dict(strength=1.0, zero=True, gains=None), as in ``compress``): the cost of the RDOQ candidate -- every
+        image quantised by rate + weighted squared error (csrc/rdoq.hip) with the weights ``compress`` would use -- plus
+        ``changed`` int64 [n], the symbols per image that are not the nearest integer (same read-back)."""
+        cfg = None if rdoq is None else self._check_rdoq_arguments("coded_cost", rdoq)
+        return self._coded_cost(x, latent_rvs, step, lam, step_offsets, weighted, cfg)
+
+    def _coded_cost(self, x, latent_rvs, step, lam, step_offsets, weighted, rdoq=None, pre=None):
+        """``coded_cost``; ``rdoq``: the checked dict of it or a ready ``entropy_coding.Rdoq``, ``pre``: ``Codec._hyper_of`` of
+        the latents' z if the caller has it."""
         self._check_step_arguments("coded_cost", step, step_offsets=step_offsets)
         if weighted:                                                  # every refusal before any launch
             if step is None and step_offsets is None:
@@ -891,11 +1020,20 @@ class Model:
         if weighted:
             block = self._position_block(h, w)
             omega = grid.position_weights(*codec.latent_shapes(h, w)[4:])
+        if isinstance(rdoq, dict):
+            rdoq = self._rdoq_tool(rdoq, n)
+        if rdoq is not None:
+            kw = dict(kw, rdoq=rdoq)
+        if pre is not None:
+            kw = dict(kw, pre=pre)
         with torch.cuda.device(self.device):
             if latent_rvs is None:
                 latent_rvs = self.infer_latent_rvs(x)
             cost_z, cost_y, px, sse = codec.latents_cost(*[rv.loc for rv in latent_rvs.uq], x, **kw)
             rows = [torch.zeros_like(cost_y) if cost_z is None else cost_z, cost_y, sse]
+            if rdoq is not None:
+                rows.append(rdoq.changed.to(cost_y.dtype))
+            at = len(rows) * n                                        # where the per-image rows end
             parts = [torch.stack(rows).to(torch.float64).flatten()]   # integers below 2^53: exact
             if weighted:                                              # uint32 -> float64 through int64: exact
                 blocks = ops.block_sse(x, px, block)
@@ -908,14 +1046,16 @@ class Model:
         out = dict(bits_z=host[:n] / 65536.0, bits_y=host[n:2 * n] / 65536.0, sse=host[2 * n:3 * n], lam=float(self._scheduled_rd_lambda))
         if lam is not None:
             out["lam"] = step_lambdas(1.0, [0] * n, lam)                   # the checks of rd_lambda: positive, finite, one per image
+        if rdoq is not None:
+            out["changed"] = np.rint(host[3 * n:4 * n]).astype(np.int64)
         out["bits"] = out["bits_z"] + out["bits_y"]
         out["D"] = out["sse"] / float(h * w * c)
         if ssim:
-            out["msssim"] = ops.image_quality_finish(host[3 * n:].reshape(tuple(sums.shape)), counts, single)
+            out["msssim"] = ops.image_quality_finish(host[at:].reshape(tuple(sums.shape)), counts, single)
             out["D"] = 1.0 - out["msssim"]
         out["J"] = out["bits"] / float(h * w) + out["lam"] * out["D"]
         if weighted:
-            out["sse_blocks"] = np.rint(host[3 * n:]).astype(np.int64).reshape(tuple(blocks.shape))
+            out["sse_blocks"] = np.rint(host[at:]).astype(np.int64).reshape(tuple(blocks.shape))
             out["D_w"] = weighted_distortion(out["sse_blocks"], omega, h * w * c)
             out["J"] = out["bits"] / float(h * w) + out["lam"] * out["D_w"]
         return out

@@ -1403,6 +1403,58 @@ def step_map_symbols(y, hyper, base_ids, kmap, lut):
     return sym, tid
 
 
+def _check_rdoq(y, weight, enable, where):
+    """``weight`` float32 [c] and ``enable`` int32 [n] on the latents' device (csrc/rdoq.hip)."""
+    n, c = y.shape[0], y.shape[-1]
+    if not (isinstance(weight, torch.Tensor) and weight.dtype == torch.float32 and tuple(weight.shape) == (c,) and weight.is_contiguous()
+            and weight.device == y.device):
+        raise ValueError(f"{where}: weight float32 [{c}] on the latents' device, one per channel")
+    if not (isinstance(enable, torch.Tensor) and enable.dtype == torch.int32 and tuple(enable.shape) == (n,) and enable.is_contiguous()
+            and enable.device == y.device):
+        raise ValueError(f"{where}: enable int32 [{n}] on the latents' device, one per image")
+
+
+def _rdoq_outputs(y, base_ids, want_changed):
+    sym = torch.empty(y.shape, dtype=torch.int32, device=y.device)
+    changed = torch.empty((y.shape[0],), dtype=torch.int32, device=y.device) if want_changed else None
+    return sym, torch.empty_like(base_ids), changed
+
+
+def rdoq_symbols(y, hyper, base_ids, inv_step, shift, weight, enable, flags, tables, want_changed=True):
+    """``step_symbols`` with the symbol chosen by rate + weighted squared error (csrc/rdoq.hip, rule in csrc/rdoq_rules.h): per
+    element of an image with enable != 0 whose nearest integer s0 is not 0, the candidate among s0, s0 - sign(s0) and (``flags`` &
+    1) 0 with the smallest J = weight[channel] * (u - s)^2 + cost_q(s), u = (y - mu) * inv_step, every operation one float32
+    rounding; a later candidate wins only on strict <.  ``weight`` float32 [c] in cost_q units (2^-16 bit) per squared symbol-unit
+    error, ``enable`` int32 [n], on the device; ``tables``: the coder's device tables (entropy_coding.DeviceTables of the scale
+    ladder).  -> (symbols int32, table ids as ``step_symbols`` writes them, changed int32 [n] = the elements written != s0, or
+    None).  With every enable 0: ``step_symbols``, bit for bit."""
+    n, hw, c, stride = _check_step_inputs(y, hyper, (inv_step, shift))
+    if base_ids.dtype != torch.int16 or tuple(base_ids.shape) != tuple(y.shape) or not base_ids.is_contiguous() \
+            or inv_step.dtype != torch.float32 or shift.dtype != torch.int32:
+        raise ValueError("rdoq_symbols: base_ids int16 (uint16 storage) like y, inv_step float32, shift int32")
+    _check_rdoq(y, weight, enable, "rdoq_symbols")
+    sym, tid, changed = _rdoq_outputs(y, base_ids, want_changed)
+    capi.call("sntc_rdoq_symbols", _ptr(y), _ptr(hyper), n, hw, c, stride, _ptr(base_ids), _ptr(inv_step), _ptr(shift), _ptr(weight),
+              _ptr(enable), int(flags), _ptr(tables.meta), tables.ntables, tables.total, _ptr(tables.cost_q), _ptr(sym), _ptr(tid),
+              _ptr(changed), _stream())
+    return sym, tid, changed
+
+
+def rdoq_map_symbols(y, hyper, base_ids, kmap, lut, weight, enable, flags, tables, want_changed=True):
+    """``rdoq_symbols`` with one ladder index per latent POSITION: ``kmap`` / ``lut`` as in ``step_map_symbols``.  With every
+    enable 0: ``step_map_symbols``, bit for bit; with a constant map: ``rdoq_symbols`` at that index."""
+    n, hw, c, stride = _check_step_inputs(y, hyper, ())
+    _check_step_map(y, kmap, lut, "rdoq_map_symbols")
+    if base_ids.dtype != torch.int16 or tuple(base_ids.shape) != tuple(y.shape) or not base_ids.is_contiguous():
+        raise ValueError("rdoq_map_symbols: base_ids int16 (uint16 storage) like y")
+    _check_rdoq(y, weight, enable, "rdoq_map_symbols")
+    sym, tid, changed = _rdoq_outputs(y, base_ids, want_changed)
+    capi.call("sntc_rdoq_map_symbols", _ptr(y), _ptr(hyper), n, hw, c, stride, _ptr(base_ids), _ptr(kmap), _ptr(lut), _ptr(weight),
+              _ptr(enable), int(flags), _ptr(tables.meta), tables.ntables, tables.total, _ptr(tables.cost_q), _ptr(sym), _ptr(tid),
+              _ptr(changed), _stream())
+    return sym, tid, changed
+
+
 def dequant_step_map(symbols, hyper, kmap, lut):
     """y_hat = fma(lut[0, k + 32], symbols, mu) at k = kmap[image, position]: ``dequant_step`` with one index per position."""
     n, hw, c, stride = _check_step_inputs(symbols, hyper, ())
