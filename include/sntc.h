@@ -708,6 +708,34 @@ int sntc_residual_table_ids(const uint8_t* base, const uint8_t* choice, int n, i
 int sntc_residual_apply(const uint8_t* base, const int32_t* q, int n, int h, int w, int c, int max_error, uint8_t* out,
                         int32_t* out_of_range, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Tiled files (csrc/tiles.hip, rule in csrc/tile_rules.h; wire format 9, DESIGN.md 4.7 "tiled files").  The reference has no
+ *   bitstream at all (mshyper/models.py:246-251: compression=False), so it has no tiles either; these two entry points are the
+ *   pixel ends of a file whose picture is cut into independently coded, overlapping tiles.  Per axis, for a length L, a tile
+ *   size T and an overlap O (T >= 4, T % 4 == 0, 0 <= O <= min(T / 4, 1024)), in integers:
+ *     R = max(1, L div T) tiles; the core of tile r is [r T, (r + 1) T), the last core runs to L (length in [T, 2 T))
+ *     extent(r) = the core grown by O on each interior side, clipped to [0, L)
+ *     extents r and r + 1 meet exactly in the band [(r + 1) T - O, (r + 1) T + O); bands are disjoint
+ *     at band offset j tile r + 1 weighs 2 j + 1, tile r weighs 4 O - (2 j + 1), denominator 4 O; elsewhere weight 1 over 1
+ *     a 2-D weight is the product of the axis weights, D = Dy Dx, value = (sum_t w_t v_t + D / 2) div D
+ *   Neither allocates or synchronises.
+ * ------------------------------------------------------------------------------------------------------- */
+/* out float [ntiles][th][tw][c] = x[image][y0 : y0 + th][x0 : x0 + tw][:] for the tiles of one shape class; x float [n][H][W][c].
+ * rects int32 [ntiles][3] = (image, y0, x0) ON THE HOST: checked here -- a rect that leaves the image is refused with
+ * SNTC_ERR_BAD_SHAPE before any launch -- and handed to the kernel as arguments, 256 tiles per launch.  16-byte copies where
+ * the rows of both sides are aligned for them, coalesced dwords otherwise.  th tw c < 2^31. */
+int sntc_tiles_extract(const float* x, int n, int H, int W, int c, const int32_t* rects, int ntiles, int th, int tw, float* out,
+                       void* stream);
+/* out uint8 [n][rh][rw][c] = the window [ry, ry + rh) x [rx, rx + rw) of the picture the tiles make, every value written once
+ * from the 1, 2 or 4 tiles that cover its pixel, blended by the integer rule above: no atomics on pixels, no accumulator, the
+ * same bytes from any launch.  tile_ptrs: a device array of n R C device pointers, (image, tile row, tile column) order, each to
+ * that tile's uint8 [extent height][extent width][c] or NULL for a tile that was not decoded.  A pixel that needs a NULL tile is
+ * written as 0 and counted in missing int32 [1] on the device (zeroed by the call); a NULL tile the window does not touch is
+ * never read.  out may start at any byte.  1 <= c <= 4, n <= 65535.  Refused with SNTC_ERR_BAD_SHAPE before
+ * any launch: a null argument, a tile / overlap outside the rule, a window that leaves the picture. */
+int sntc_tiles_assemble(const uint8_t* const* tile_ptrs, int n, int H, int W, int c, int tile, int overlap, int ry, int rx, int rh,
+                        int rw, uint8_t* out, int32_t* missing, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * SSIM / MS-SSIM statistics (eval-only quality metrics, reference mshyper/models.py:321-336 ->
  *   tf.image.ssim / tf.image.ssim_multiscale).  Images are float NHWC holding pixel

@@ -34,6 +34,13 @@ Wire format v8 = a v3 / v5 / v7 blob wrapped in a coded pixel residual layer (cs
   decoder has.  The decoder adds q (2 max_error + 1) to the base and clips: every pixel within max_error of the original, the
   original itself at 0.  ``split_residual(blob)[0]`` is the base file; a nested v8 base and a v4 base are refused.
 
+Wire format v9 = a TILED file (tiling.py, csrc/tiles.hip, DESIGN.md 4.7 "tiled files"): the picture cut into overlapping tiles that
+  are coded as the images of ordinary v3 / v5 batches, so a reader decodes only the tiles a window needs:
+  b"SNTC" u16 version (low byte 9; high byte = the arithmetic tag) | u16 n | u32 H | u32 W | u16 tile | u16 overlap | u16 nblobs |
+  nblobs x (u16 th, u16 tw, u32 count, u32 bytes) | the inner blobs, each a complete v3 / v5 file of ``count`` images of th x tw.
+  Tiles in (image, row, column) order, grouped by shape in order of first appearance, 256 to an inner blob at the most; the
+  parser recomputes the whole table from (n, H, W, tile, overlap) (``tiling.parse_v9``).  Written only by ``compress(x, tile=...)``.
+
 The factorized-prior model (factorized/models.py) has ONE latent and no hyper-synthesis: ``FactorizedCodec``, wire format v4
   b"SNTC" u16 version (low byte 4; high byte = the arithmetic tag, as above) | u16 n | u32 H | u32 W | u16 C | u16 h | u16 w |
   u16 segments | u8 lanes | u8 0 | u32 len_words[n * segments] | payload
@@ -54,6 +61,8 @@ import torch
 
 from . import _capi as capi
 from . import ops
+from . import tiling
+from .tiling import VERSION_TILED, select_images, tile_index      # wire format 9: the host half
 
 PRECISION = 16
 TOTAL = 1 << PRECISION
@@ -1405,6 +1414,7 @@ class Codec:
 
     def __init__(self, model):
         self.m = model
+        self.last_decompress_report = None
         dev = model.device
         nl = len(model._prior_num_filters) + 1
         with torch.cuda.device(dev):
@@ -1635,7 +1645,7 @@ class Codec:
         sz, sy = _segments(ez), _segments(ey)
         return 32 * (sz * _lanes(-(-ez // sz)) + sy * _lanes(-(-ey // sy)))
 
-    def compress(self, x, step=None, target_bpp=None, step_offsets=None, target_psnr=None) -> bytes:
+    def compress(self, x, step=None, target_bpp=None, step_offsets=None, target_psnr=None, tile=None, overlap=16) -> bytes:
         """``step`` / ``step_offsets``: as in ``compress_latents``; with ``target_bpp`` the offsets are added to the index rate
         control chooses, the candidates are priced over the map (``ladder_cost(..., step_offsets=...)``), and each image's
         prediction counts ``map_bits`` = 24 per maximal run of its offsets (an upper bound on the records written: clipping
@@ -1647,8 +1657,12 @@ class Codec:
         with the FEWEST predicted bits among those whose decoded pixels reach the target (integer SSE <= 255^2 3 H W /
         10^(target / 10), ``ladder_distortion``: exactly what ``decompress`` will give, the 16-bit escape aside), STEP_MIN where
         none does (``select_quality``).  One encoder pass, the ladder launches of both sides, one read-back, the coding launches;
-        the file is that of ``step=`` the chosen indexes.  ``last_report``: ``select_quality``'s rows (+ map_bits with offsets)."""
+        the file is that of ``step=`` the chosen indexes.  ``last_report``: ``select_quality``'s rows (+ map_bits with offsets).
+        ``tile`` = T (with ``overlap``, default 16): a tiled file, wire format 9 (``compress_tiled``); only ``step`` may accompany it."""
         m = self.m
+        if tile is not None:
+            tiling.refuse_with_tile(target_bpp=target_bpp, target_psnr=target_psnr, step_offsets=step_offsets)
+            return self.compress_tiled(x, tile, overlap, step)
         x = m._as_device_images(x)
         n, H, W = x.shape[0], int(x.shape[1]), int(x.shape[2])
         if sum(v is not None for v in (step, target_bpp, target_psnr)) > 1:
@@ -1690,6 +1704,108 @@ class Codec:
         map_bits = None if offsets is None else MAP_RECORD_BITS * count_runs(offsets)
         return select_steps(bits, budget_bits, ladder, map_bits), pre
 
+    def check_tiling(self, tile, overlap):
+        """``tile`` / ``overlap`` of the public entry points -> (T, O) as ints; ValueError unless T is a multiple of the model's
+        downsample factor with T >= 64 and 0 <= O <= T / 4."""
+        return tiling.check_tiling(tile, overlap, self.m.downsample_factor)
+
+    def compress_tiled(self, x, tile, overlap=16, step=None) -> bytes:
+        """``compress(x, tile=T, overlap=O, step=...)``: the tiled file of x, wire format 9.  The picture is cut into the tiles of
+        ``tiling.tile_plan`` (extents of T + up to 2 O pixels; the last of an axis up to 2 T - 1 + O), each inner blob of at most
+        ``tiling.TILE_BATCH`` same-shaped tiles is one extract launch (``ops.tiles_extract``) and one ``_launch_latents`` on a
+        lane of its own, and ONE ``_finish`` -- two read-backs -- ends all of them, as in ``compress_many``.  Every inner blob is,
+        byte for byte, ``compress(those tiles, step=...)``.  ``step``: an int, or one per image, applied to all of that image's
+        tiles (inner blobs of wire format 5).  Every refusal comes before anything is enqueued, the upload of a host ``x``
+        included.  The inner blobs share the pool's first ``ops.SIDE_POOL_MIN`` lanes in turn -- a large picture has hundreds of
+        them, and a stream each would only share hardware queues --; the tiles and latents of ALL of them are resident until
+        the one ``_finish``, about the footprint of ``compress(x)`` itself plus the extracted tiles."""
+        m = self.m
+        T, O = self.check_tiling(tile, overlap)
+        shape = tuple(int(v) for v in getattr(x, "shape", ()))
+        if len(shape) not in (3, 4):
+            raise ValueError(f"compress: images [n, H, W, 3] or [H, W, 3], not shape {shape}")
+        n, H, W = (1,) * (4 - len(shape)) + shape[:len(shape) - 1]
+        if not (1 <= n <= self.MAX_IMAGES and 1 <= H <= self.MAX_SIDE and 1 <= W <= self.MAX_SIDE):
+            raise ValueError(f"compress: {n} images of {H} x {W} are beyond what a file holds")
+        steps = None if step is None else check_steps(step, n)
+        g, plan, _ = tiling.tile_plan(n, H, W, T, O)
+        if len(plan) > 0xffff or max(b["th"] for b in plan) > 0xffff or max(b["tw"] for b in plan) > 0xffff:
+            raise ValueError("compress: the tile plan is beyond what a tiled file holds")
+        grids = [self._grid(None if steps is None else [steps[i] for i, _, _ in b["tiles"]], None, len(b["tiles"]), b["th"], b["tw"])
+                 for b in plan]
+        x = m._as_device_images(x)
+        assert tuple(x.shape[:3]) == (n, H, W)
+        with torch.cuda.device(m.device):
+            main, pool = ops.lanes(min(len(plan), ops.SIDE_POOL_MIN), m.device)
+            lanes = [pool[k % len(pool)] for k in range(len(plan))]
+            jobs = []
+            for st, b, grid in zip(lanes, plan, grids):
+                rects = [(i, g["rows"][r][2], g["cols"][c][2]) for i, r, c in b["tiles"]]
+                with ops.fork(main, st, reads=(x,)):
+                    lat = m.infer_latent_rvs(ops.tiles_extract(x, rects, b["th"], b["tw"]))
+                    jobs.append(self._launch_latents(lat.uq[0].loc.contiguous(), lat.uq[1].loc.contiguous(), (b["th"], b["tw"]), grid))
+            for st, j in zip(lanes, jobs):
+                ops.join(main, st, made=[t for grp in j["groups"] for t in grp])
+            inner = self._finish(jobs)
+        return tiling.pack_v9(ARITH[m._precision], n, H, W, T, O, inner)
+
+    def _refuse_tiled(self, blobs, what):
+        for b in blobs:
+            if tiling.is_tiled(b):
+                raise capi.SntcError(capi.ERR_UNSUPPORTED, f"{what}: the bitstream is a tiled file (wire format {VERSION_TILED}); {what} reads "
+                                     "untiled files -- decompress it and compress the pixels again")
+
+    def _decompress_tiled(self, blobs, regions):
+        """``decompress_many`` with tiled files among ``blobs``; ``regions[k]``: the window (y0, x0, h, w) of tiled blob k, or
+        None.  The inner blobs that hold a needed tile -- cut down to the needed tiles with ``select_images`` where only some
+        are -- and the untiled files go through ONE ``decompress_many`` call, whose pipelining then applies to all of them; one
+        assemble launch per tiled file follows (``ops.tiles_assemble``; its count of missing pixels is read back once per
+        file).  Fills ``last_decompress_report``: one dict(tiles_total, tiles_decoded, bytes_total, bytes_read) per tiled file."""
+        arith = ARITH[self.m._precision]
+        self.last_decompress_report = None                         # a refused file leaves no earlier call's report behind
+        flat, plans = [], []
+        for blob, region in zip(blobs, regions):
+            if not tiling.is_tiled(blob):
+                if region is not None:
+                    raise ValueError("decompress: region needs a tiled file (compress(x, tile=...)); this bitstream is not tiled")
+                plans.append(len(flat))
+                flat.append(blob)
+                continue
+            blob = bytes(blob)
+            hd = tiling.parse_v9(blob, arith)
+            g = hd["grid"]
+            window = (0, 0, hd["H"], hd["W"]) if region is None else tuple(int(v) for v in region)
+            need = set(tiling.region_tiles(g, window))                         # ValueError on a window outside the picture
+            at, read = {}, hd["head_bytes"]
+            for b in hd["blobs"]:
+                keep = [j for j, (_, r, c) in enumerate(b["tiles"]) if (r, c) in need]
+                if not keep:
+                    continue                                                   # an untouched inner blob is never uploaded
+                part = select_images(blob[b["at"]:b["at"] + b["bytes"]], keep)
+                read += len(part)
+                for j, k in enumerate(keep):
+                    at[b["tiles"][k]] = (len(flat), j)
+                flat.append(part)
+            plans.append(dict(hd=hd, window=window, at=at, report=dict(tiles_total=hd["n"] * g["R"] * g["C"], tiles_decoded=len(at),
+                                                                      bytes_total=len(blob), bytes_read=read)))
+        decoded = self.decompress_many(flat)
+        out = []
+        with torch.cuda.device(self.m.device):
+            for p in plans:
+                if not isinstance(p, dict):
+                    out.append(decoded[p])
+                    continue
+                hd, g = p["hd"], p["hd"]["grid"]
+                tiles = []
+                for i in range(hd["n"]):
+                    for r in range(g["R"]):
+                        for c in range(g["C"]):
+                            k, j = p["at"].get((i, r, c), (None, None))
+                            tiles.append(None if k is None else decoded[k][j])
+                out.append(ops.tiles_assemble(tiles, hd["n"], hd["H"], hd["W"], RESIDUAL_CHANNELS, hd["tile"], hd["overlap"], p["window"]))
+        self.last_decompress_report = [p["report"] for p in plans if isinstance(p, dict)]
+        return out
+
     def compress_many(self, xs):
         """``compress`` for several batches (e.g. one per image size of a set) -> their bitstreams, in order, byte for byte what one
         ``compress`` per batch returns.  The batches' transforms and entropy-coding launches run side by side on the library's
@@ -1706,10 +1822,18 @@ class Codec:
             raise capi.SntcError(capi.ERR_UNSUPPORTED, f"bitstream version {blob[4]} (quantisation steps) decodes in precision 'fp32' only")
         return hd
 
-    def decompress(self, blob: bytes):
-        return self.decompress_many([blob])[0]
+    def decompress(self, blob: bytes, region=None):
+        """``region`` = (y0, x0, h, w): that window of a TILED file (wire format 9) -> uint8 [n, h, w, 3], equal to the same window
+        of the full decode; only the tiles whose extents meet it are decoded (``_decompress_tiled``).  ValueError on an untiled
+        file or a window that leaves the picture.  ``last_decompress_report``: dict(tiles_total, tiles_decoded, bytes_total,
+        bytes_read) after a tiled file, None after an untiled one (``decompress_many``: a LIST with one such dict per tiled file
+        of the call, in order; None where the call held no tiled file)."""
+        out = self.decompress_many([blob], regions=None if region is None else [region])[0]
+        if self.last_decompress_report is not None:
+            self.last_decompress_report = self.last_decompress_report[0]
+        return out
 
-    def decompress_many(self, blobs):
+    def decompress_many(self, blobs, regions=None):
         """Several bitstreams (e.g. one per batch shape of a set) -> their pixel batches, in order.  An entropy-decoding launch
         is a handful of lone waves whose time is a latency (one wave per stream, ~0.4 us per step of 64 symbols whatever the
         batch), so the launches of ALL blobs' hyper-latents run side by side on streams of their own; then the blobs are
@@ -1723,6 +1847,14 @@ class Codec:
         m = self.m
         if not blobs:
             return []
+        if regions is not None or any(tiling.is_tiled(b) for b in blobs):
+            # wire format 9: its inner blobs join the others in ONE call of this function, an assemble launch per tiled file follows
+            blobs = list(blobs)
+            regions = [None] * len(blobs) if regions is None else list(regions)
+            if len(regions) != len(blobs):
+                raise ValueError(f"decompress_many: {len(regions)} regions for {len(blobs)} bitstreams")
+            return self._decompress_tiled(blobs, regions)
+        self.last_decompress_report = None                         # no tiled file in this call (``_decompress_tiled`` sets its own after it)
         # wire format 8: the base file inside goes through the pipeline below unchanged, its residual layer follows the syntheses
         layers = [None] * len(blobs)
         if any(is_residual(b) for b in blobs):
@@ -1874,6 +2006,7 @@ class Codec:
         m = self.m
         delta = check_max_error(max_error)
         require_fp32(m._precision, "the residual layer")
+        self._refuse_tiled([blob], "add_residual")
         self._refuse_layered([blob], "add_residual")
         x = self._layer_images(blob, x, "add_residual")
         with torch.cuda.device(m.device):
@@ -1901,6 +2034,7 @@ class Codec:
         if not deltas:
             raise ValueError("residual_bits: no max_error")
         require_fp32(m._precision, "the residual layer")
+        self._refuse_tiled([blob], "residual_bits")
         self._refuse_layered([blob], "residual_bits")
         x = m._as_device_images(x)
         with torch.cuda.device(m.device):
@@ -1937,6 +2071,7 @@ class Codec:
         if (shift is None) == (target_bpp is None):
             raise ValueError("transcode: exactly one of shift and target_bpp")
         require_fp32(m._precision, "transcode")
+        self._refuse_tiled(blobs, "transcode")
         self._refuse_layered(blobs, "transcode")
         if not blobs:
             return []
@@ -2075,6 +2210,7 @@ class FactorizedCodec:
 
     def __init__(self, model):
         self.m = model
+        self.last_decompress_report = None
         dev = model.device
         nl = len(model._prior_num_filters) + 1
         with torch.cuda.device(dev):

@@ -682,7 +682,7 @@ class Model:
         return self._codec
 
     def compress(self, x, itinf=None, step=None, target_bpp=None, step_offsets=None, target_psnr=None, max_error=None,
-                 rdoq=None) -> bytes:
+                 rdoq=None, tile=None, overlap=16) -> bytes:
         """Images -> self-contained bitstream (rANS over the integer CDF tables of both entropy models).
         ``itinf`` = dict(steps, seed=0, check_every=None): refine the latents of THESE images by SGA iterative inference first
         (``initialize_itinf`` + ``steps`` x ``itinf_train_step(x, seed=seed, fetch=False)`` under the model's own tau / learning-rate
@@ -760,7 +760,27 @@ class Model:
         nearest integer), bits_plain, bits_rdoq, sse_plain, sse_rdoq, J_plain, J_rdoq, J_chosen, lam, quant_step.  Combines
         with ``step``, ``step_offsets`` and ``max_error``; excludes ``itinf``, ``target_bpp`` and ``target_psnr`` (ValueError: the
         ladder kernels price nearest-integer symbols).  Mean-scale hyperprior models in precision 'fp32' with MSE only
-        (NotImplementedError)."""
+        (NotImplementedError).
+        ``tile`` = T (a multiple of ``downsample_factor``, T >= 64) with ``overlap`` = O (0 <= O <= T / 4, default 16): a TILED
+        file, wire format 9 (entropy_coding.Codec.compress_tiled, DESIGN.md 4.7 "tiled files").  The picture is cut into tiles
+        whose cores are T x T (the last of an axis runs to the edge: T .. 2 T - 1) and whose extents reach O pixels into their
+        neighbours; the tiles are coded independently, as the images of ordinary batches, and ``decompress`` blends them across
+        the 2 O-wide seams with integer weights.  ``decompress(blob, region=(y0, x0, h, w))`` then decodes only the tiles the
+        window meets and returns exactly that window of the full decode; ``tile_index(blob)`` lists the tiles.  Only ``step`` (an
+        int, or one per image, applied to all of that image's tiles) may accompany ``tile``: ``itinf``, ``target_bpp``,
+        ``target_psnr``, ``step_offsets``, ``max_error`` and ``rdoq`` are a ValueError before anything is enqueued, and a
+        factorized-prior model refuses ``tile`` (NotImplementedError).  Without ``tile`` nothing changes: the file of today,
+        byte for byte."""
+        if tile is not None:
+            if self.factorized:
+                raise NotImplementedError("compress(tile): tiled files hold wire format 3 / 5 inner blobs; mean-scale hyperprior models only")
+            from .. import tiling
+            tiling.refuse_with_tile(itinf=itinf, target_bpp=target_bpp, target_psnr=target_psnr, step_offsets=step_offsets,
+                                    max_error=max_error, rdoq=rdoq)
+            tiling.check_tiling(tile, overlap, self.downsample_factor)
+            if step is not None:
+                self._check_step_arguments("compress", step)
+            return self._get_codec().compress(x, step=step, tile=tile, overlap=overlap)
         if max_error is not None:
             self._check_residual_arguments("compress", max_error)
         self._check_step_arguments("compress", step, target_bpp, itinf, step_offsets, target_psnr=target_psnr)
@@ -1164,14 +1184,39 @@ class Model:
         the set costs two host synchronisations (entropy_coding.Codec.compress_many).  Same bytes as one ``compress`` per batch."""
         return self._get_codec().compress_many(list(xs))
 
-    def decompress(self, blob: bytes):
-        """Bitstream -> uint8 pixels [n, H, W, 3]; bit-identical to ``decode(encode(x))``."""
-        return self._get_codec().decompress(blob)
+    def decompress(self, blob: bytes, region=None):
+        """Bitstream -> uint8 pixels [n, H, W, 3]; bit-identical to ``decode(encode(x))``.  A tiled file (wire format 9,
+        ``compress(x, tile=...)``) decodes to its tiles blended across their seams.  ``region`` = (y0, x0, h, w), tiled files
+        only: -> uint8 [n, h, w, 3], exactly that window of the full decode, from the tiles whose extents meet it alone -- the
+        other inner blobs are never uploaded; ValueError on an untiled file or a window that leaves the picture.
+        ``last_decompress_report``: dict(tiles_total, tiles_decoded, bytes_total, bytes_read) after a tiled file, None after
+        any other."""
+        codec = self._get_codec()
+        self.last_decompress_report = None
+        if region is None:
+            out = codec.decompress(blob)
+        elif self.factorized:
+            raise ValueError("decompress: region needs a tiled file; a factorized-prior model writes none")
+        else:
+            out = codec.decompress(blob, region=region)
+        self.last_decompress_report = getattr(codec, "last_decompress_report", None)
+        return out
+
+    def tile_index(self, blob: bytes):
+        """The grid of a tiled file and, per tile, its extent, inner blob and index within it (``tiling.tile_index``); host only."""
+        from ..tiling import tile_index
+        return tile_index(blob)
 
     def decompress_many(self, blobs):
         """Several bitstreams -> their pixel batches; the entropy-decoding launches of all of them run side by side
-        (entropy_coding.Codec.decompress_many).  Same pixels as one ``decompress`` per blob."""
-        return self._get_codec().decompress_many(list(blobs))
+        (entropy_coding.Codec.decompress_many).  Same pixels as one ``decompress`` per blob.  Tiled files (wire format 9) may be
+        mixed in freely; ``last_decompress_report`` is then a LIST with one dict(tiles_total, tiles_decoded, bytes_total,
+        bytes_read) per tiled file of the call, in order, and None where the call held none."""
+        codec = self._get_codec()
+        self.last_decompress_report = None
+        out = codec.decompress_many(list(blobs))
+        self.last_decompress_report = getattr(codec, "last_decompress_report", None)
+        return out
 
     def transcode(self, blob: bytes, shift=None, target_bpp=None) -> bytes:
         """A bitstream of this model -> the bitstream of a coarser quantisation step, from the file alone: no pixels, no analysis,

@@ -1211,6 +1211,64 @@ def to_pixels(x_hat, h, w):
     return px
 
 
+def tiles_extract(x, rects, th, tw):
+    """The tiles of ONE shape class cut out of ``x`` float32 [n, H, W, c] (csrc/tiles.hip): ``rects`` = (image, y0, x0) per tile,
+    on the host -> float32 [len(rects), th, tw, c], out[t] = x[image, y0:y0 + th, x0:x0 + tw].  A rect that leaves the image is
+    refused by the library before any launch.  No host synchronisation."""
+    _check_nhwc(x)
+    n, H, W, c = x.shape
+    r = np.ascontiguousarray(np.asarray(rects, dtype=np.int32).reshape(-1, 3))
+    th, tw = int(th), int(tw)
+    if len(r) < 1 or th < 1 or tw < 1:
+        raise ValueError("tiles_extract: at least one rect and a tile of at least 1 x 1")
+    out = torch.empty((len(r), th, tw, c), dtype=torch.float32, device=x.device)
+    capi.call("sntc_tiles_extract", _ptr(x), n, H, W, c, C.c_void_p(r.ctypes.data), len(r), th, tw, _ptr(out), _stream())
+    return out
+
+
+def tiles_assemble(tiles, n, H, W, c, tile, overlap, region=None, out=None, check=True):
+    """Decoded tiles -> the picture, or a window of it, with blended seams (csrc/tiles.hip, the rule of csrc/tile_rules.h).
+    ``tiles``: n R C entries in (image, tile row, tile column) order (``tiling.tile_grid``), each the tile's contiguous uint8
+    [extent height, extent width, c] on the device -- a view of a decoded batch will do -- or None for a tile that was not
+    decoded; every shape is checked against the grid here, the kernel trusts it.  ``region`` = (y0, x0, h, w), default the whole
+    picture -> uint8 [n, h, w, c] (``out``: write there instead; it may start at any byte).  A window pixel that needs a missing
+    tile: SntcError (``check``; one read-back) -- with ``check=False`` -> (out, the count int32 [1] on the device) and no
+    synchronisation.  The tiles must stay alive until the launch has run: the caller's stream orders that where it made them."""
+    from . import tiling
+    g = tiling.tile_grid(H, W, tile, overlap)
+    y0, x0, h, w = (0, 0, int(H), int(W)) if region is None else (int(v) for v in region)
+    tiling.region_tiles(g, (y0, x0, h, w))                               # ValueError on a window that leaves the picture
+    tiles = list(tiles)
+    if len(tiles) != n * g["R"] * g["C"]:
+        raise ValueError(f"tiles_assemble: {len(tiles)} tiles for {n} images of {g['R']} x {g['C']}")
+    dev, ptrs = None, np.zeros(len(tiles), np.int64)
+    for k, t in enumerate(tiles):
+        if t is None:
+            continue
+        (_, _, a0, a1), (_, _, b0, b1) = g["rows"][k // g["C"] % g["R"]], g["cols"][k % g["C"]]
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (a1 - a0, b1 - b0, c)
+                and t.is_contiguous() and (dev is None or t.device == dev)):
+            raise ValueError(f"tiles_assemble: tile {k} must be a contiguous uint8 {(a1 - a0, b1 - b0, c)} tensor on the device")
+        dev = t.device
+        ptrs[k] = t.data_ptr()
+    if dev is None:
+        raise ValueError("tiles_assemble: no tile was decoded")
+    if out is None:
+        out = torch.empty((n, h, w, c), dtype=torch.uint8, device=dev)
+    elif not (out.dtype == torch.uint8 and tuple(out.shape) == (n, h, w, c) and out.is_contiguous() and out.device == dev):
+        raise ValueError(f"tiles_assemble: out must be a contiguous uint8 {(n, h, w, c)} tensor on the tiles' device")
+    table = torch.from_numpy(ptrs).to(dev)
+    missing = torch.empty((1,), dtype=torch.int32, device=dev)
+    capi.call("sntc_tiles_assemble", _ptr(table), n, int(H), int(W), c, int(tile), int(overlap), y0, x0, h, w, _ptr(out), _ptr(missing),
+              _stream())
+    if not check:
+        return out, missing
+    lost = int(missing.item())
+    if lost:
+        raise capi.SntcError(capi.ERR_BAD_SHAPE, f"tiles_assemble: {lost} pixels of the window need a tile that was not decoded")
+    return out
+
+
 def pixels_sse(x, x_hat, want_pixels=False):
     """uint8 quantisation of both images + per-image integer SSE.  x_hat may be spatially larger
     (the crop of unpad_images is fused)."""
